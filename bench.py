@@ -27,6 +27,7 @@ and, at N = 1, outside the timed region (all skipped by --no-parity):
   latency                -- the reference's own measurement regime (batch 1, its profiler's clip lengths): encode + decode of
                             B = 1 / 8 clips of 1 / 10 / 32 s, ms per call, RTF, top-3 kernels (other_configs.{mimi,dac}.batch1_latency: 1 x 1 s eager
                             and through the wrappers' opt-in hipGraph replay, graph=True; the LSTM codecs decline it, audiocodecs_amd/codec.py)
+--dump-outputs DIR writes what the last timed step returned (tokens, decoded waveform) as DIR/<name>.npy (dump_outputs()).
 Nothing inside an `if rank == 0` block issues a collective (tests/test_bench_contract.py checks the source for it), and the
 flow from the warm-ups to the JSON line is `run()`, which tests/test_bench_flow_gloo.py executes at world size 2 over gloo.
 """
@@ -574,6 +575,36 @@ def contract_line(label, ncb, world, steps, warmup, dt, audio_s, B, seconds, dty
     return out
 
 
+DUMP_WHOLE_BYTES = 16 << 20    # --dump-outputs: an array up to this size is written whole ...
+DUMP_SAMPLE = 1 << 21          # ... a larger one as this many elements at fixed, seeded flat positions
+DUMP_SEED = 20250101
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: the arrays the timed path handed its caller in the last timed step (`toks` from sig_to_toks, `sig` from
+    toks_to_sig), as DIR/<name>.npy -- floating arrays of up to 32 bits as float32, everything else (the int64 tokens) as float64,
+    which holds them exactly.  An array over DUMP_WHOLE_BYTES is written as a sample: DUMP_SAMPLE elements of its flattened form at
+    positions drawn once with DUMP_SEED (sorted), and the positions themselves as DIR/<name>_sample_index.npy.  The inputs and the
+    weights are seeded, so two builds run with the same arguments can be compared file by file.  Returns {file: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    files, total = {}, 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" and a.dtype.itemsize <= 4 else np.float64)
+        parts = {name: a}
+        if a.nbytes > DUMP_WHOLE_BYTES:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLE, replace=False))
+            parts = {name: a.reshape(-1)[idx], f"{name}_sample_index": idx.astype(np.float64)}
+        for fn, v in parts.items():
+            total += v.nbytes
+            if total > DUMP_LIMIT_BYTES:
+                raise RuntimeError(f"--dump-outputs: {total} bytes would exceed the {DUMP_LIMIT_BYTES}-byte limit")
+            np.save(os.path.join(out_dir, fn + ".npy"), v)
+            files[fn + ".npy"] = list(v.shape)
+    return files
+
+
 def run(args, codec, cfg, sd, sig, sig_cpu, rank, world, dist, device):
     """Everything after set-up, for any codec object with sig_to_toks / toks_to_sig / profile_kernels and any process group (RCCL on
     the GPU; tests/test_bench_flow_gloo.py drives it at world size 2 over gloo with a stub codec on CPU tensors).
@@ -585,11 +616,16 @@ def run(args, codec, cfg, sd, sig, sig_cpu, rank, world, dist, device):
     B, T = sig.shape[0], sig.shape[1]
     sync = torch.cuda.synchronize if device.type == "cuda" else (lambda: None)
 
+    last = {}   # --dump-outputs: what the caller of the timed path receives, kept from the newest step (references only, no copy)
+
     def step():
         toks = codec.sig_to_toks(sig)
         if dist is not None:
             gather_tokens(toks, force=True)
-        return codec.toks_to_sig(toks)
+        rec = codec.toks_to_sig(toks)
+        if args.dump_outputs:
+            last["toks"], last["sig"] = toks, rec
+        return rec
 
     def local_step():   # the same work without the collective: for rank-local diagnostics outside the timed region
         return codec.toks_to_sig(codec.sig_to_toks(sig))
@@ -616,6 +652,9 @@ def run(args, codec, cfg, sd, sig, sig_cpu, rank, world, dist, device):
                  "f32 (GEMM-shaped kernels and LSTM products: operands as two scaled fp16 planes, 3 partial products, fp32 accumulate -- split16.h)")
         out = contract_line(label, ncb, world, args.steps, args.warmup, dt, audio_s, B, args.seconds, dtype,
                             {"whole_path": wp, "roofline": roof, "kernels": kernel_rows(stats, args.steps)})
+        if args.dump_outputs:   # before any untimed extra runs the codec again
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, last)
+        last.clear()
         extras = not args.no_parity and device.type == "cuda"
         with torch.no_grad():
             if extras and args.codec == "encodec":
@@ -744,7 +783,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE.json configs 3-5 (DAC, Mimi, WavTokenizer) that travel in the same JSON line")
     ap.add_argument("--no-exact", action="store_true", help="skip the exact-fp32-product twin of the headline figure")
     ap.add_argument("--no-latency", action="store_true", help="skip the B = 1 / B = 8 latency table (the reference's own measurement regime)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: tokens and decoded waveform) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed, seeded sample of a larger array)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(argv, gpus):
