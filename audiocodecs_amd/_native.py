@@ -164,6 +164,7 @@ EXPORTS = {
     "ac_debug_bounds": (_i, [_vp, C.POINTER(C.c_float), _i]),
     "ac_debug_trace": (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
     "ac_debug_split_row": (_i, [_vp, _i, _vp, _vp]),
+    "ac_debug_tap_route": (_i, [_vp, C.c_char_p, _i, C.POINTER(C.c_int32)]),
     "ac_debug_capture": (_i, [_vp, _vp, _sz]),
     "ac_debug_set": (_i, [_vp, C.c_char_p, _i]),
     "ac_debug_captured": (_sz, [_vp]),

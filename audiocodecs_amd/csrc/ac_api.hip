@@ -2,6 +2,7 @@
 // core.hip (shared + EnCodec) and mimi_path.hip / dac_path.hip / wavtok_path.hip (one codec each, with its ac_*_create); core.h
 // has the map.  gfx950 only.
 #include "core.h"
+#include "tap_route.h"
 
 // ---------------------------------------------------------------------------------------------
 // exported entry points
@@ -542,6 +543,39 @@ int ac_debug_split_row(const float* w, int n, uint16_t* hi, uint16_t* lo) {
         if (lo) lo[k] = t[1];
     }
     return s;
+}
+
+int ac_debug_tap_route(const ac_tap_route_query* q, char* name, int cap, int32_t* flags) {
+    if (!q || q->struct_size != (int32_t)sizeof(ac_tap_route_query) || q->nseg < 1 || q->nseg > 2 || !name || cap < 1 || !flags) return AC_EINVAL;
+    // pointer fields -> addresses route_tap tests for null / alignment (never dereferenced)
+    auto ptr = [](int32_t v) { return reinterpret_cast<float*>((uintptr_t)(v == 0 ? 0 : v == 1 ? 256 : 260)); };
+    TapGemmParams p{};
+    p.nseg = q->nseg;
+    for (int i = 0; i < q->nseg; ++i) {
+        const ac_tap_seg_query& a = q->seg[i];
+        TapSeg& g = p.seg[i];
+        g.x = ptr(a.x);
+        g.rel_len = ptr(a.rel_len);
+        g.L = a.L, g.cin = a.cin, g.s = a.s, g.J = a.J, g.dil = a.dil, g.pad = a.pad, g.lim = a.lim, g.kofs = a.kofs, g.elu = a.elu;
+        g.bs = a.bs, g.ts = a.ts;
+    }
+    p.B = q->B, p.M = q->M, p.N = q->N, p.Ktot = q->Ktot;
+    p.w = ptr(q->w), p.y = ptr(q->y), p.y_elu = ptr(q->y_elu), p.scale = ptr(q->scale), p.res = ptr(q->res), p.alpha = ptr(q->alpha);
+    p.gelu = q->gelu, p.tanh_out = q->tanh_out, p.n_valid = q->n_valid;
+    p.y_bs = q->y_bs, p.y_rs = q->y_rs, p.res_rs = q->res_rs, p.y_off = q->y_off, p.y_len = q->y_len;
+    TapRouteInputs in;
+    in.w6 = q->has_w6 != 0;
+    in.winv = q->has_winv != 0;
+    in.want_rowmode = q->want_rowmode != 0;
+    in.want_rows = q->want_rows != 0;
+    in.gemm_fp32 = q->gemm_fp32 != 0;
+    ac_handle::DevSwitches dev;
+    dev.tap_epi_staged = q->tap_epi_staged, dev.tap_dil = q->tap_dil, dev.tap_pick = q->tap_pick;
+    dev.tap8 = q->tap8, dev.tap8_form = q->tap8_form, dev.tap8_spread = q->tap8_spread;
+    const TapRoute r = route_tap(p, in, dev);
+    std::snprintf(name, (size_t)cap, "%s", r.name);
+    *flags = (r.rowmode ? 1 : 0) | (r.epi_direct ? 2 : 0) | (r.reject_taps ? 4 : 0) | (r.spread ? 8 : 0);
+    return AC_OK;
 }
 
 int ac_debug_bounds(const ac_handle* h, float* out, int cap) {

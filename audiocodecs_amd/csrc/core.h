@@ -1,5 +1,5 @@
 // Host-side internals shared by the translation units of libaudiocodecs_amd.so:
-//   core.hip        the shared machinery (weight packing, split16 pools, tap-GEMM dispatch, fused-block / LSTM / codebook launchers,
+//   core.hip        the shared machinery (weight packing, split16 pools, tap-GEMM dispatch (its kernel choice: tap_route.h), fused-block / LSTM / codebook launchers,
 //                   workspace planning) and the EnCodec encoder / decoder; owns every kernel the codecs share
 //   mimi_path.hip, dac_path.hip, wavtok_path.hip   one codec each: plan, finalize, forward passes, its own kernels, its ac_*_create
 //   ac_api.hip      the extern "C" entry points of include/audiocodecs_amd.h

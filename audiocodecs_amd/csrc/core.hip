@@ -9,6 +9,7 @@
 #include "tap_gemm4.h"
 #include "tap_gemm6.h"
 #include "tap_gemm8.h"
+#include "tap_route.h"
 #include "thin.h"
 #include "rb_fused.h"
 #include "rb_fused6.h"
@@ -174,29 +175,113 @@ const unsigned* amax_plus(ac_handle* h, hipStream_t st, const Act& x, float add,
 }
 
 
-template <int WGM, int WGN, int WM, int WN, bool VEC>
-void launch_tap(const TapGemmParams& p0, hipStream_t st) {
-    TapGemmParams p = p0;
+// ---- run_tap's launchers: one per kernel family, a flat switch over the arrangements route_tap (tap_route.h) can return.  Each opens
+// the launch's profile record (`name`: the route's name + the prof_detail shape suffix) and, above 64 KB, its dynamic-LDS opt-in.
+
+template <int WGM, int WGN, int WM, int WN>
+static int launch_tap(ac_handle* h, hipStream_t st, TapGemmParams p, TapFamily f, const char* name, double flops, double bytes) {
+    ProfScope ps(h, st, name, flops, bytes);
+    if (f == TapFamily::tap4) {
+        using Cfg = Tap4Cfg<WGM, WGN, WM, WN>;
+        p.mtiles = cdiv(p.M, Cfg::BM);
+        p.ntiles = cdiv(p.N, Cfg::BN);
+        if (int rc = ensure_lds(h, reinterpret_cast<const void*>(tap_gemm4_kernel<WGM, WGN, WM, WN>), Cfg::lds_bytes)) return rc;
+        const long long blocks = (long long)p.B * p.mtiles * p.ntiles;
+        hipLaunchKernelGGL((tap_gemm4_kernel<WGM, WGN, WM, WN>), dim3((unsigned)blocks), dim3(Cfg::NT), Cfg::lds_bytes, st, p);
+        return AC_OK;
+    }
     constexpr int BM = WGM * WM * 16, BN = WGN * WN * 16;
     p.mtiles = cdiv(p.M, BM);
     p.ntiles = cdiv(p.N, BN);
     const size_t lds = tap_gemm_lds_bytes<WGM, WGN, WM, WN>();
     const long long blocks = (long long)p.B * p.mtiles * p.ntiles;
-    hipLaunchKernelGGL((tap_gemm_kernel<WGM, WGN, WM, WN, VEC>), dim3((unsigned)blocks), dim3(WGM * WGN * 64), lds, st, p);
+    if (f == TapFamily::vec) hipLaunchKernelGGL((tap_gemm_kernel<WGM, WGN, WM, WN, true>), dim3((unsigned)blocks), dim3(WGM * WGN * 64), lds, st, p);
+    else hipLaunchKernelGGL((tap_gemm_kernel<WGM, WGN, WM, WN, false>), dim3((unsigned)blocks), dim3(WGM * WGN * 64), lds, st, p);
+    return AC_OK;
 }
 
+// tap_gemm4 (exact fp32 products, aligned operands) and tap_gemm (vector / scalar loads)
+static int launch_tap_fp32(ac_handle* h, hipStream_t st, const TapGemmParams& p, const TapRoute& r, const char* name, double flops, double bytes) {
+    switch (r.key()) {
+    case tap_key(4, 1, 2, 1): return launch_tap<4, 1, 2, 1>(h, st, p, r.family, name, flops, bytes);
+    case tap_key(4, 1, 2, 2): return launch_tap<4, 1, 2, 2>(h, st, p, r.family, name, flops, bytes);
+    case tap_key(2, 2, 2, 2): return launch_tap<2, 2, 2, 2>(h, st, p, r.family, name, flops, bytes);
+    case tap_key(2, 2, 4, 3): return launch_tap<2, 2, 4, 3>(h, st, p, r.family, name, flops, bytes);
+    case tap_key(2, 2, 4, 4): return launch_tap<2, 2, 4, 4>(h, st, p, r.family, name, flops, bytes);
+    }
+    return fail(h, AC_EINVAL, "run_tap: no instantiation of %s", r.name);
+}
 
-template <int WGM, int WGN, int WM, int WN>
-int launch_tap4(ac_handle* h, const TapGemmParams& p0, hipStream_t st) {
-    using Cfg = Tap4Cfg<WGM, WGN, WM, WN>;
-    TapGemmParams p = p0;
+template <int WGM, int WGN, int WMT, int WN, int HALO>
+static int launch_tap6(ac_handle* h, hipStream_t st, TapGemmParams& p, const __bf16* w6, const char* name, double flops, double bytes) {
+    using Cfg = Tap6Cfg<WGM, WGN, WMT, WN, HALO>;
     p.mtiles = cdiv(p.M, Cfg::BM);
-    p.ntiles = cdiv(p.N, Cfg::BN);
-    if (int rc = ensure_lds(h, reinterpret_cast<const void*>(tap_gemm4_kernel<WGM, WGN, WM, WN>), Cfg::lds_bytes)) return rc;
+    p.ntiles = p.N / Cfg::BN;
     const long long blocks = (long long)p.B * p.mtiles * p.ntiles;
-    const size_t lds = Cfg::lds_bytes;
-    hipLaunchKernelGGL((tap_gemm4_kernel<WGM, WGN, WM, WN>), dim3((unsigned)blocks), dim3(Cfg::NT), lds, st, p);
+    if (int rc = ensure_lds(h, reinterpret_cast<const void*>(tap_gemm6_kernel<WGM, WGN, WMT, WN, 2, HALO>), Cfg::lds_for(2))) return rc;
+    ProfScope ps(h, st, name, flops, bytes);
+    hipLaunchKernelGGL((tap_gemm6_kernel<WGM, WGN, WMT, WN, 2, HALO>), dim3((unsigned)blocks), dim3(Cfg::NT), Cfg::lds_for(2), st, p, w6);
     return AC_OK;
+}
+
+// tap_gemm6; the dilated-slab instantiations only where route_tap can pick them (WN >= 2, or the 128 x 32 tile of a long contraction)
+static int launch_tap6_family(ac_handle* h, hipStream_t st, TapGemmParams& p, const TapRoute& r, const __bf16* w6, const char* name, double flops, double bytes) {
+    if (r.family == TapFamily::tap6_dil) {
+        switch (r.key()) {
+        case tap_key(1, 4, 4, 2): return launch_tap6<1, 4, 4, 2, T6_DIL_HALO>(h, st, p, w6, name, flops, bytes);
+        case tap_key(1, 4, 4, 1): return launch_tap6<1, 4, 4, 1, T6_DIL_HALO>(h, st, p, w6, name, flops, bytes);
+        case tap_key(2, 2, 2, 3): return launch_tap6<2, 2, 2, 3, T6_DIL_HALO>(h, st, p, w6, name, flops, bytes);
+        case tap_key(4, 1, 1, 3): return launch_tap6<4, 1, 1, 3, T6_DIL_HALO>(h, st, p, w6, name, flops, bytes);
+        }
+    } else {
+        switch (r.key()) {
+        case tap_key(1, 4, 4, 2): return launch_tap6<1, 4, 4, 2, 7>(h, st, p, w6, name, flops, bytes);
+        case tap_key(1, 8, 4, 1): return launch_tap6<1, 8, 4, 1, 7>(h, st, p, w6, name, flops, bytes);
+        case tap_key(1, 4, 4, 1): return launch_tap6<1, 4, 4, 1, 7>(h, st, p, w6, name, flops, bytes);
+        case tap_key(2, 2, 2, 3): return launch_tap6<2, 2, 2, 3, 7>(h, st, p, w6, name, flops, bytes);
+        case tap_key(4, 1, 1, 3): return launch_tap6<4, 1, 1, 3, 7>(h, st, p, w6, name, flops, bytes);
+        case tap_key(2, 2, 2, 1): return launch_tap6<2, 2, 2, 1, 7>(h, st, p, w6, name, flops, bytes);
+        }
+    }
+    return fail(h, AC_EINVAL, "run_tap: no instantiation of %s", r.name);
+}
+
+template <int WGM, int WGN, int WMT, int WN, bool RM, bool J1, bool SP>
+static int launch_tap8(ac_handle* h, hipStream_t st, TapGemmParams& p, const __bf16* w6, const char* name, double flops, double bytes) {
+    using Cfg = Tap8Cfg<WGM, WGN, WMT, WN>;
+    p.mtiles = cdiv(p.M, Cfg::BM);
+    p.ntiles = p.N / Cfg::BN;
+    const long long blocks = (long long)p.B * p.mtiles * p.ntiles;
+    ProfScope ps(h, st, name, flops, bytes);
+    if (int rc = ensure_lds(h, reinterpret_cast<const void*>(tap_gemm8_kernel<WGM, WGN, WMT, WN, RM, J1, SP>), Cfg::lds_bytes)) return rc;
+    hipLaunchKernelGGL((tap_gemm8_kernel<WGM, WGN, WMT, WN, RM, J1, SP>), dim3((unsigned)blocks), dim3(Cfg::NT), Cfg::lds_bytes, st, p, w6);
+    return AC_OK;
+}
+
+// tap_gemm8: three tile forms x (row mode | one tap | taps) x SPREAD -- every one reachable through the developer switches tap8_form / tap8_spread
+static int launch_tap8_family(ac_handle* h, hipStream_t st, TapGemmParams& p, const TapRoute& r, const __bf16* w6, const char* name, double flops, double bytes) {
+    constexpr int RJ = TK_RM | TK_J1, J = TK_J1, S = TK_SPREAD;
+    switch (r.key()) {
+    case tap_key(2, 4, 4, 2, RJ): return launch_tap8<2, 4, 4, 2, true, true, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 4, 2, RJ | S): return launch_tap8<2, 4, 4, 2, true, true, true>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 4, 2, J): return launch_tap8<2, 4, 4, 2, false, true, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 4, 2, J | S): return launch_tap8<2, 4, 4, 2, false, true, true>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 4, 2): return launch_tap8<2, 4, 4, 2, false, false, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 4, 2, S): return launch_tap8<2, 4, 4, 2, false, false, true>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 2, 2, RJ): return launch_tap8<2, 4, 2, 2, true, true, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 2, 2, RJ | S): return launch_tap8<2, 4, 2, 2, true, true, true>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 2, 2, J): return launch_tap8<2, 4, 2, 2, false, true, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 2, 2, J | S): return launch_tap8<2, 4, 2, 2, false, true, true>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 2, 2): return launch_tap8<2, 4, 2, 2, false, false, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(2, 4, 2, 2, S): return launch_tap8<2, 4, 2, 2, false, false, true>(h, st, p, w6, name, flops, bytes);
+    case tap_key(4, 2, 2, 2, RJ): return launch_tap8<4, 2, 2, 2, true, true, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(4, 2, 2, 2, RJ | S): return launch_tap8<4, 2, 2, 2, true, true, true>(h, st, p, w6, name, flops, bytes);
+    case tap_key(4, 2, 2, 2, J): return launch_tap8<4, 2, 2, 2, false, true, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(4, 2, 2, 2, J | S): return launch_tap8<4, 2, 2, 2, false, true, true>(h, st, p, w6, name, flops, bytes);
+    case tap_key(4, 2, 2, 2): return launch_tap8<4, 2, 2, 2, false, false, false>(h, st, p, w6, name, flops, bytes);
+    case tap_key(4, 2, 2, 2, S): return launch_tap8<4, 2, 2, 2, false, false, true>(h, st, p, w6, name, flops, bytes);
+    }
+    return fail(h, AC_EINVAL, "run_tap: no instantiation of %s", r.name);
 }
 
 
@@ -232,18 +317,19 @@ TapSeg make_seg(const Act& x, int s, int J, int pad /*PAD_**/, int extra, int ko
 }
 
 
+// Every conv / linear layer: route_tap picks the kernel, then the split16 operands it needs get their amax slots / row words (in
+// launch order: the slots come out in the same sequence run to run), then the family's launcher runs it.
 int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p) {
-    bool vec = (p.Ktot % 4 == 0) && aligned16(p.w);
-    bool fast = vec && (p.N % 4 == 0) && (p.y_rs % 4 == 0) && (p.y_bs % 4 == 0) && (!p.y || aligned16(p.y)) &&
-                (!p.y_elu || aligned16(p.y_elu)) && (long long)p.N * p.Ktot * 4 < (1LL << 31);
-    for (int i = 0; i < p.nseg; ++i) {
-        const TapSeg& s = p.seg[i];
-        vec = vec && (s.cin % 4 == 0) && (s.ts % 4 == 0) && (s.bs % 4 == 0) && (s.kofs % 4 == 0) && aligned16(s.x);
-        fast = fast && ((s.s * s.cin) % KC == 0) && (s.ts == s.cin || s.s == 1) && !s.rel_len && !s.elu &&
-               ((long long)(s.L - 1) * s.ts + s.cin) * 4 < (1LL << 31);
-        if (s.J > 8) return fail(h, AC_EINVAL, "conv with %d taps exceeds the kernel limit of 8", s.J);
-    }
-    fast = fast && vec;
+    const auto w6_it = h->w6_of.find((size_t)(p.w - h->blob));
+    const auto iv = h->winv_of.find((size_t)(p.w - h->blob));
+    TapRouteInputs in;
+    in.w6 = w6_it != h->w6_of.end();
+    in.winv = iv != h->winv_of.end();
+    in.want_rowmode = p.amax_rows != 0;
+    in.want_rows = p.amax_out_rows != nullptr;    // (any non-null value is a request)
+    in.gemm_fp32 = h->gemm_fp32;
+    const TapRoute r = route_tap(p, in, h->dev);
+    if (r.reject_taps) return fail(h, AC_EINVAL, "conv with %d taps exceeds the kernel limit of 8", r.reject_taps);
     double kk = 0, inb = 0;
     for (int i = 0; i < p.nseg; ++i) {
         kk += (double)p.seg[i].J * p.seg[i].s * p.seg[i].cin;
@@ -251,36 +337,18 @@ int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p) {
     }
     const double flops = 2.0 * p.B * (double)p.M * p.N * kk;
     const double bytes = inb + (double)p.B * p.M * p.N * 4.0 * ((p.y ? 1 : 0) + (p.y_elu ? 1 : 0)) + (double)p.N * p.Ktot * 4.0;
-    // split-operand kernel on the bf16 pipe (tap_gemm6.h) where the shape allows and the weights were packed for it
-    const __bf16* w6 = nullptr;
-    if (fast && !h->gemm_fp32 && (p.N % 64 == 0 || p.N % 96 == 0)) {
-        auto it = h->w6_of.find((size_t)(p.w - h->blob));
-        bool ok6 = it != h->w6_of.end();
-        for (int i = 0; ok6 && i < p.nseg; ++i) ok6 = p.seg[i].kofs % 32 == 0;
-        if (ok6) w6 = reinterpret_cast<const __bf16*>(h->blob + it->second);
-    }
-    int rc = AC_OK;
-    char shape[64] = "";
-    if (h->prof && h->prof_detail)
+    std::string name = r.name;
+    if (h->prof && h->prof_detail && r.family != TapFamily::scalar && r.family != TapFamily::vec) {
+        char shape[64];
         std::snprintf(shape, sizeof shape, " B%d M%d N%d K%d J%d s%d%s", p.B, p.M, p.N, (int)kk, p.seg[0].J, p.seg[0].s, p.seg[0].dil == 1 ? "" : p.seg[0].dil == 3 ? " d3" : " d9");
-#define TAP_CASE(WGM, WGN, WM, WN)                                                                          \
-    do {                                                                                                    \
-        if (fast) {                                                                                         \
-            ProfScope ps(h, st, (std::string("tap_gemm4_kernel<" #WGM ", " #WGN ", " #WM ", " #WN ">") + shape).c_str(), flops, bytes); \
-            rc = launch_tap4<WGM, WGN, WM, WN>(h, p, st);                                                   \
-        } else if (vec) {                                                                                   \
-            ProfScope ps(h, st, "tap_gemm_kernel<" #WGM ", " #WGN ", " #WM ", " #WN ", true>", flops, bytes); \
-            launch_tap<WGM, WGN, WM, WN, true>(p, st);                                                      \
-        } else {                                                                                            \
-            ProfScope ps(h, st, "tap_gemm_kernel<" #WGM ", " #WGN ", " #WM ", " #WN ", false>", flops, bytes); \
-            launch_tap<WGM, WGN, WM, WN, false>(p, st);                                                     \
-        }                                                                                                   \
-    } while (0)
-    const bool want_rows = p.amax_out_rows != nullptr;    // (any non-null value is a request)
+        name += shape;
+    }
     p.amax_out_rows = nullptr;
-    const int want_rowmode = p.amax_rows;
     p.amax_rows = 0;
-    if (w6) {
+    int rc;
+    if (r.family == TapFamily::scalar || r.family == TapFamily::vec || r.family == TapFamily::tap4) {
+        rc = launch_tap_fp32(h, st, p, r, name.c_str(), flops, bytes);
+    } else {
         p.clk = h->clk_dev;
 #ifdef T6_TRACE   // developer trace builds only: clock / stamps of ONE layer shape "M,N,K"
         if (const char* ts = std::getenv("AC_TRACE_SHAPE")) {
@@ -288,12 +356,7 @@ int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p) {
             if (std::sscanf(ts, "%d,%d,%d", &tm, &tn, &tk) == 3 && !((tm == 0 || tm == p.M) && tn == p.N && tk == (int)kk)) p.clk = nullptr;   // (M = 0: any M)
         }
 #endif
-        auto iv = h->winv_of.find((size_t)(p.w - h->blob));
-        // (row mode only on the caller's request -- the linear layers over merged token matrices: a conv that merely happens to
-        // run with one clip must scale like the same conv in a batch, or a clip's result would depend on the batch size)
-        const bool rowmode = want_rowmode && iv != h->winv_of.end() && p.B == 1 && p.nseg == 1 && p.seg[0].J == 1 && p.seg[0].s == 1 && p.seg[0].pad == 0 &&
-                             p.seg[0].lim >= p.M && p.seg[0].L >= p.M && p.y_off == 0;
-        if (rowmode) {                    // split16.h row mode: a linear layer over a merged row matrix -- one scale per row
+        if (r.rowmode) {                  // split16.h row mode: a linear layer over a merged row matrix -- one scale per row
             TapSeg& sg = p.seg[0];
             if (!(sg.amax && sg.amax_n == -p.M)) {
                 unsigned* rm = rowmax_new(h, st, p.M, false);
@@ -304,11 +367,11 @@ int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p) {
             }
             p.amax_rows = 1;
             p.winv = h->blob + iv->second;
-            if (want_rows) {              // the caller asked for the output's row words: a fresh, zeroed array
+            if (r.rows_out) {             // the caller asked for the output's row words: a fresh, zeroed array
                 p.amax_out_rows = rowmax_new(h, st, p.M, true);
                 if (!p.amax_out_rows) return fail(h, AC_ENOMEM, "the workspace pool's row ring is too small for %d rows", p.M);
             }
-        } else if (iv != h->winv_of.end()) {     // split16.h: every operand tensor needs its amax; the output reports its own
+        } else if (in.winv) {             // split16.h: every operand tensor needs its amax; the output reports its own
             for (int i = 0; i < p.nseg; ++i) {
                 TapSeg& sg = p.seg[i];
                 sg.amax = amax_of(h, st, sg.x, sg.bs, sg.ts, sg.L, sg.cin, p.B, sg.amax_n == p.B ? sg.amax : nullptr);
@@ -316,144 +379,13 @@ int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p) {
             }
             p.winv = h->blob + iv->second;
             p.amax_out = amax_new(h);
-            // plain conv outputs store straight from the accumulators (tap_gemm6.h); AC_TAP_EPI=staged: the LDS-staged epilogue
-            const bool staged_env = h->dev.tap_epi_staged != 0;       // (ac_debug_set "tap_epi_staged": a test flips it)
-            // (ELU flavour without a residual, Snake flavour with or without one: the combinations the four codecs produce)
-            p.epi_direct = !staged_env && !p.gelu && !p.scale && !p.tanh_out && p.y_off == 0 && p.y_len == 0 &&
-                           (!p.res || (p.alpha && (long long)p.M * p.res_rs * 4 < 0x7fffffffLL && p.res_rs * 4 < (1 << 20))) && (!p.alpha || p.y_elu) &&
-                           (p.n_valid == 0 || p.n_valid == p.N) && (p.alpha ? p.N < 128 && p.N % 32 == 0 : p.N % 128 == 0) &&      // (measured: Snake / residual layers of 128+ channels are faster through the LDS-staged 16-byte rows)
-                           (long long)p.M * p.y_rs * 4 < 0x7fffffffLL && p.y_rs * 4 < (1 << 20);
+            p.epi_direct = r.epi_direct;
         }
         p.stagger = h->dev.tap_stagger;
-        const bool dil_env = h->dev.tap_dil != 0;                 // developer / tests: 0 -> slab reload per tap
-        const bool dil_slab = dil_env && !p.amax_rows && p.nseg == 1 && p.seg[0].dil != 1   /* (the wide-slab instantiation has no row mode: CAN_ROWMODE, tap_gemm6.h) */ && p.seg[0].s == 1 && (p.seg[0].J - 1) * p.seg[0].dil <= T6_DIL_HALO;
-#define TAP6_LAUNCH(WGM, WGN, WMT, WN, NP)                                                                              \
-    do {                                                                                                                \
-        if ((rc = ensure_lds(h, reinterpret_cast<const void*>(tap_gemm6_kernel<WGM, WGN, WMT, WN, NP>), Cfg6::lds_for(NP)))) return rc; \
-        ProfScope ps(h, st, (std::string("tap_gemm6_kernel<" #WGM ", " #WGN ", " #WMT ", " #WN ", " #NP ">") + shape).c_str(), flops, bytes); \
-        hipLaunchKernelGGL((tap_gemm6_kernel<WGM, WGN, WMT, WN, NP>), dim3((unsigned)blocks), dim3(Cfg6::NT), Cfg6::lds_for(NP), st, p, w6); \
-    } while (0)
-#define TAP6_CASE(WGM, WGN, WMT, WN)                                                                                    \
-    do {                                                                                                                \
-        using Cfg6 = Tap6Cfg<WGM, WGN, WMT, WN>;                                                                        \
-        p.mtiles = cdiv(p.M, Cfg6::BM);                                                                                 \
-        p.ntiles = p.N / Cfg6::BN;                                                                                      \
-        const long long blocks = (long long)p.B * p.mtiles * p.ntiles;                                                  \
-        if (p.winv && dil_slab && (WN >= 2 || (WGM == 1 && WGN == 4 && kk >= 2048))) {                                  \
-            /* dilated taps out of one wide slab (tap_gemm6.h: T6_DIL_HALO); measured per arrangement on DAC's layers: the 128 x 32  \
-               tile loses its third workgroup per CU to the larger slab and gains only for long contractions, 64 x 32 tiles lose */ \
-            using Cfg6D = Tap6Cfg<WGM, WGN, WMT, WN, T6_DIL_HALO>;                                                      \
-            if ((rc = ensure_lds(h, reinterpret_cast<const void*>(tap_gemm6_kernel<WGM, WGN, WMT, WN, 2, T6_DIL_HALO>), Cfg6D::lds_for(2)))) return rc; \
-            ProfScope ps(h, st, (std::string("tap_gemm6_kernel<" #WGM ", " #WGN ", " #WMT ", " #WN ", 2, dil>") + shape).c_str(), flops, bytes); \
-            hipLaunchKernelGGL((tap_gemm6_kernel<WGM, WGN, WMT, WN, 2, T6_DIL_HALO>), dim3((unsigned)blocks), dim3(Cfg6D::NT), Cfg6D::lds_for(2), st, p, w6); \
-        } else TAP6_LAUNCH(WGM, WGN, WMT, WN, 2);                                                                       \
-    } while (0)
-        // tap_gemm8.h: the 256-row, 8-wave kernel with the weight stage through an LDS-DMA ring and activation chunks requested two
-        // chunks ahead -- one segment, taps inside one slab, N % 128 == 0 (the same arithmetic in the same order: bit-identical outputs)
-        {
-            const TapSeg& s0 = p.seg[0];
-            const bool can8 = p.winv && p.nseg == 1 && (s0.J - 1) * s0.dil <= 7 && !(s0.dil != 1 && s0.s != 1) && p.N % 128 == 0 && (s0.s * s0.cin) % 32 == 0 &&
-                              (!p.epi_direct || p.N % 128 == 0);
-            const int want8 = h->dev.tap8;       // 0: never, 1: wherever the shape allows (developer A/B), -1: cost model
-            bool use8 = false;
-            if (can8 && want8 != 0) {
-                // tile forms (8 waves each): 1 = 256 x 256 (2 x 4 waves of 128 x 64), 3 = 128 x 256 (2 x 4 waves of 64 x 64) where 256-row
-                // tiles would leave CUs idle or rows empty (M = 750: three tiles per clip; M = 125), 2 = 256 x 128 (4 x 2 waves of 64 x 64) for
-                // N % 256 != 0.  Score = rate relative to form 1 (EnCodec / Mimi / DAC layers, profiles/r4_tapgemm8.md) x how evenly the
-                // workgroups fill the 256 CUs x the share of tile rows that exist.
-                auto fill8 = [&](int bm, int bn) {
-                    const double w = (double)p.B * cdiv(p.M, bm) * (p.N / bn) / 256.0;
-                    return w / std::ceil(w) * ((double)p.M / ((double)cdiv(p.M, bm) * bm));
-                };
-                const double sc1 = p.N % 256 == 0 ? 1.00 * fill8(256, 256) : 0.0;
-                const double sc3 = p.N % 256 == 0 ? 0.90 * fill8(128, 256) : 0.0;
-                int form = sc1 >= sc3 ? 1 : 3;
-                bool model = (form == 1 ? sc1 : sc3) >= 0.80;
-                if (p.N % 256 != 0) {      // 64 x 64 wave tiles over 128 columns lose to tap_gemm6's three workgroups per CU except on long contractions
-                    form = 2;
-                    model = kk >= 3072 && fill8(256, 128) >= 0.70;
-                }
-                // tiny launches (the batch-1 / batch-8 regime: at most 64 tiles of 128 x 128): every workgroup has a CU of its own and walks its K
-                // loop at one memory round trip per stage -- the ring's deeper look-ahead is what counts (1.39 -> 1.34 ms per 1 s call)
-                if ((double)p.B * cdiv(p.M, 128) * (p.N / 128) <= 64.0) {
-                    form = p.N % 256 == 0 ? 3 : 2;
-                    model = true;
-                }
-                if (h->dev.tap8_form >= 1 && h->dev.tap8_form <= 3 && (h->dev.tap8_form == 2 || p.N % 256 == 0)) form = h->dev.tap8_form;
-                use8 = want8 >= 1 || model;
-                if (use8) {
-#define TAP8_LAUNCH_KP(WGM, WGN, WMT, WN, RM, J1, SP)                                                                    \
-    do {                                                                                                                \
-        if ((rc = ensure_lds(h, reinterpret_cast<const void*>(tap_gemm8_kernel<WGM, WGN, WMT, WN, RM, J1, SP>), Cfg8::lds_bytes))) return rc; \
-        hipLaunchKernelGGL((tap_gemm8_kernel<WGM, WGN, WMT, WN, RM, J1, SP>), dim3((unsigned)blocks), dim3(Cfg8::NT), Cfg8::lds_bytes, st, p, w6); \
-    } while (0)
-#define TAP8_LAUNCH_K(WGM, WGN, WMT, WN, RM, J1)                                                                         \
-    do {                                                                                                                \
-        /* requests dealt between the MFMA units (tap_gemm8.h SPREAD): measured per form -- 128 x 256 tiles gain, 256 x 256 are level, 256 x 128 lose */ \
-        const bool spread = h->dev.tap8_spread == 2 || (h->dev.tap8_spread == 1 && (WGM) * (WMT) * 32 == 128);         \
-        if (spread) TAP8_LAUNCH_KP(WGM, WGN, WMT, WN, RM, J1, true); else TAP8_LAUNCH_KP(WGM, WGN, WMT, WN, RM, J1, false); \
-    } while (0)
-#define TAP8_LAUNCH(WGM, WGN, WMT, WN)                                                                                   \
-    do {                                                                                                                \
-        using Cfg8 = Tap8Cfg<WGM, WGN, WMT, WN>;                                                                        \
-        p.mtiles = cdiv(p.M, Cfg8::BM);                                                                                 \
-        p.ntiles = p.N / Cfg8::BN;                                                                                      \
-        const long long blocks = (long long)p.B * p.mtiles * p.ntiles;                                                  \
-        ProfScope ps(h, st, (std::string("tap_gemm8_kernel<" #WGM ", " #WGN ", " #WMT ", " #WN ", 2>") + shape).c_str(), flops, bytes); \
-        if (s0.J == 1) { if (p.amax_rows) TAP8_LAUNCH_K(WGM, WGN, WMT, WN, true, true); else TAP8_LAUNCH_K(WGM, WGN, WMT, WN, false, true); } \
-        else           { TAP8_LAUNCH_K(WGM, WGN, WMT, WN, false, false); }   /* (row mode is a one-tap affair: run_tap's `rowmode`) */ \
-    } while (0)
-                    if (form == 1) TAP8_LAUNCH(2, 4, 4, 2);
-                    else if (form == 3) TAP8_LAUNCH(2, 4, 2, 2);
-                    else TAP8_LAUNCH(4, 2, 2, 2);
-#undef TAP8_LAUNCH_K
-#undef TAP8_LAUNCH_KP
-#undef TAP8_LAUNCH
-                    HIPCHK(h, hipGetLastError());
-                    return AC_OK;
-                }
-            }
-        }
-        // Tile / wave arrangement (measured, profiles/r2_tapgemm_variants.md).  The weight fragments come L2 -> registers and the
-        // activation slab is shared through LDS, so the CU's vector-memory path and the LDS pipe are what an arrangement must
-        // spare:  1 x 4 waves of 128 x 32 (distinct weight fragments per wave) beats 2 x 2 waves of 64 x 64 by 5-7 %;
-        // 1 x 4 waves of 128 x 64 over 256 columns (half the A-slab reads, loads and splits per MFMA; lean main loop) gains
-        // another 8-10 % where the launch still fills the chip evenly; 1 x 8 waves over 256 columns (one workgroup per CU)
-        // wins for long contractions.  Choice by a small cost model: rate of the arrangement x how evenly its workgroups
-        // fill the 256 CUs (waves of workgroups / ceil(waves)).
-        int pick = 0;   // 0: 128 columns, 1: 256 columns lean, 2: 256 columns 1 x 8
-        if (p.N % 256 == 0) {
-            const double wg256 = (double)p.B * cdiv(p.M, 128) * (p.N / 256);
-            auto fill = [](double wgs, double slots) { const double w = wgs / slots; return w / std::ceil(w); };
-            // (split16: the 128-column arrangement runs three workgroups per CU and is 6 % faster per flop than before)
-            const double s128 = p.winv ? 1.06 * fill(2.0 * wg256, 768.0) : 1.00 * fill(2.0 * wg256, 512.0);
-            const double s256 = 1.10 * fill(wg256, 512.0);
-            // (split16: 1 x 8 waves no longer beat the three-workgroup 128-column arrangement per flop -- WavTokenizer's K = 2304 layers:
-            //  4.71 ms at 128 columns, 5.43 ms with 1 x 8 waves)
-            const double s8 = (kk >= 2048 ? (p.winv ? 1.00 : 1.12) : (p.winv ? 0.85 : 0.95)) * fill(wg256, 256.0);
-            pick = s256 >= s128 && s256 >= s8 ? 1 : (s8 > s128 ? 2 : 0);
-            if (h->dev.tap_pick >= 0 && h->dev.tap_pick <= 2) pick = h->dev.tap_pick;     // developer override
-        }
-        // (256-row, 8-wave arrangements of THIS kernel -- <2,4,4,2>, <2,4,4,1> -- measured 7-12 % / 25-30 % slower per layer than
-        //  the picks below: one workgroup per CU and the old load pipeline; profiles/r4_tapgemm8.md.  tap_gemm8.h is that tile with a
-        //  pipeline built for it.)
-        if (pick == 1) TAP6_CASE(1, 4, 4, 2);
-        else if (pick == 2) TAP6_CASE(1, 8, 4, 1);
-        else if (p.N % 128 == 0) TAP6_CASE(1, 4, 4, 1);
-        else if (p.N % 192 == 0) TAP6_CASE(2, 2, 2, 3);   // DAC's 192-wide layers: a weight fragment is loaded by two waves, not four
-        else if (p.N % 96 == 0) TAP6_CASE(4, 1, 1, 3);
-        else TAP6_CASE(2, 2, 2, 1);
-#undef TAP6_CASE
-#undef TAP6_LAUNCH
-        HIPCHK(h, hipGetLastError());
-        return AC_OK;
+        const __bf16* w6 = reinterpret_cast<const __bf16*>(h->blob + w6_it->second);
+        rc = r.family == TapFamily::tap8 ? launch_tap8_family(h, st, p, r, w6, name.c_str(), flops, bytes)
+                                         : launch_tap6_family(h, st, p, r, w6, name.c_str(), flops, bytes);
     }
-    if (p.N <= 16) TAP_CASE(4, 1, 2, 1);
-    else if (p.N <= 32) TAP_CASE(4, 1, 2, 2);
-    else if (p.N <= 64) TAP_CASE(2, 2, 2, 2);
-    else if (p.N % 96 == 0 && p.N % 128 != 0) TAP_CASE(2, 2, 4, 3);   // DAC widths 96 / 192: 128-column tiles would idle a quarter of the MFMAs
-    else TAP_CASE(2, 2, 4, 4);
-#undef TAP_CASE
     if (rc) return rc;
     HIPCHK(h, hipGetLastError());
     return AC_OK;

@@ -183,6 +183,7 @@ __device__ __forceinline__ float epilogue1(const TapGemmParams& p, float v, int 
 constexpr int GEN_EXTRA = 56; // halo rows of the generic kernel's A slab: (J-1)*dil <= 6*9
 constexpr int KC = 32;        // K chunk staged per iteration
 constexpr int KCP = KC + 4;   // LDS pitch (floats): keeps 16-B alignment, spreads banks
+constexpr int T6_DIL_HALO = 56; // tap_gemm6.h: halo rows of the wide slab the dilated k7 convs read their taps from
 
 // Source value for padded time index i (may be <0 or >= L) and channel ci of item b.
 __device__ __forceinline__ long long src_index(const TapSeg& sg, int i) {

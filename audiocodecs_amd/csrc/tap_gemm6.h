@@ -37,7 +37,7 @@ constexpr int T6_PITCH = 40;        // bf16 per LDS row (32 + 8): 80-byte rows k
 // HALO: rows of the A slab beyond BM.  7 = the taps of a k <= 8 conv on consecutive rows; T6_DIL_HALO = the dilated k7 convs of
 // DAC's residual units (6 x 9 rows) read from ONE slab per chunk like any other conv, instead of a slab reload per tap
 // (13 - 22 % slower per launch, profiles/r3_tapgemm_trace.md).  The larger slab costs LDS (59 KB instead of 43 KB: two workgroups per CU).
-constexpr int T6_DIL_HALO = 56;
+// (T6_DIL_HALO is defined in tap_gemm.h: run_tap's routing, tap_route.h, reads it on the host.)
 template <int WGM, int WGN, int WMT, int WN, int HALO = 7>
 struct Tap6Cfg {
     static_assert((WGM * WGN == 4 || WGM * WGN == 8) && (WGM * WMT == 4 || WGM * WMT == 8), "4 or 8 waves, 128 or 256 rows");

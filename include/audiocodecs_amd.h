@@ -354,6 +354,33 @@ int ac_debug_trace(ac_handle* h, unsigned long long* out, int words);
  * hi = fp16_rn(w 2^s) and lo = fp16_rn(w 2^s - hi).  Returns s.  The CPU tests compare it with numpy's float16. */
 int ac_debug_split_row(const float* w, int n, uint16_t* hi, uint16_t* lo);
 
+/* Test hook (no GPU, no handle): the kernel csrc/core.hip run_tap launches for one tap-GEMM (every conv / linear layer), from
+ * the inputs its routing reads (csrc/tap_route.h route_tap).  Pointer fields take 0 = null, 1 = 16-byte aligned, 2 = set but not
+ * 16-byte aligned; the switch fields start from the defaults of ac_debug_set's keys of the same names (tap_dil = 1, tap_pick = -1,
+ * tap8 = -1, tap8_spread = 1, the others 0).  Writes the profile record name without the shape suffix (e.g.
+ * "tap_gemm6_kernel<1, 4, 4, 1, 2>") to name[cap] and sets *flags: 1 = split16 row mode, 2 = direct epilogue, 4 = rejected
+ * (more than 8 taps; name empty), 8 = tap_gemm8's requests dealt between its MFMA units (SPREAD).  Returns AC_OK, or AC_EINVAL
+ * for a bad query. */
+typedef struct ac_tap_seg_query {
+    int32_t x;                         /* pointer: the segment's input                             */
+    int32_t rel_len;                   /* pointer: per-clip relative lengths                       */
+    int32_t L, cin, s, J, dil, pad, lim, kofs, elu;
+    int64_t bs, ts;                    /* batch / time-step strides (floats)                      */
+} ac_tap_seg_query;
+typedef struct ac_tap_route_query {
+    int32_t struct_size;               /* = sizeof(ac_tap_route_query)                             */
+    int32_t B, M, N, Ktot, nseg;       /* nseg: 1 or 2                                             */
+    ac_tap_seg_query seg[2];
+    int32_t w, y, y_elu, scale, res, alpha;          /* pointers                                   */
+    int32_t gelu, tanh_out, n_valid;
+    int64_t y_bs, y_rs, res_rs, y_off, y_len;
+    int32_t has_w6, has_winv;          /* the packer made split16 planes / per-row scales of the weights */
+    int32_t want_rowmode, want_rows;   /* the caller asks for row mode / for the output's row words */
+    int32_t gemm_fp32;                 /* exact-fp32 products                                      */
+    int32_t tap_epi_staged, tap_dil, tap_pick, tap8, tap8_form, tap8_spread;
+} ac_tap_route_query;
+int ac_debug_tap_route(const ac_tap_route_query* q, char* name, int cap, int32_t* flags);
+
 /* Which LSTM path the handle uses (SYNCHRONISES the device; tests / diagnostics): 1 = the persistent single-launch kernel
  * (D = 512, 2 layers, 256-CU device; opt out with the environment variable AC_LSTM=step), 0 = one launch per
  * time step, AC_EHIP = a persistent launch failed since the handle was created (a bounded wait expired, or the launch
