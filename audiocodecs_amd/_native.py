@@ -155,6 +155,10 @@ EXPORTS = {
     "ac_quantizer_workspace_bytes": (_sz, [_vp, _i, _i]),
     "ac_quantize_ws": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ac_dequantize_ws": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ac_mimi_stream_state_bytes": (_sz, [_vp, _i]),
+    "ac_mimi_stream_reset": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
+    "ac_mimi_stream_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "ac_mimi_stream_encode": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ac_embs": (_i, [_vp, _i, _vp, _vp]),
     "ac_embs_projected": (_i, [_vp, _i, _vp, _vp]),
     "ac_resample": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -2,6 +2,7 @@
 //   core.hip        the shared machinery (weight packing, split16 pools, tap-GEMM dispatch (its kernel choice: tap_route.h), fused-block / LSTM / codebook launchers,
 //                   workspace planning) and the EnCodec encoder / decoder; owns every kernel the codecs share
 //   mimi_path.hip, dac_path.hip, wavtok_path.hip   one codec each: plan, finalize, forward passes, its own kernels, its ac_*_create
+//   mimi_stream.hip streaming Mimi encode: the stream state, one push's launch sequence, its kernels and its ac_mimi_stream_* entry points
 //   ac_api.hip      the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
@@ -217,6 +218,7 @@ struct ac_handle {
     bool gemm_fp32 = false;         // AC_PRECISION_FP32_EXACT (or AC_GEMM=fp32): exact-product kernels only
                                     // (false: split16.h -- fp32-fidelity arithmetic of the matrix kernels, two fp16 planes, 3 products)
     std::map<size_t, size_t> winv_of;   // split16 images: float offset of a packed fp32 matrix -> offset of its per-row 2^-s
+    std::map<const void*, int> mimi_streams;   // mimi_stream.hip: state buffers ac_mimi_stream_reset prepared on this handle -> their B
     // amax slots (split16.h): [slot][amax_B] words, handed out in launch order, cleared at the start of every pass
     unsigned* amax_buf = nullptr;
     int amax_B = 0, amax_next = 0;

@@ -18,7 +18,7 @@ from .codec import Codec
 from .config import MIMI_24KHZ, MimiConfig
 from .encodec import _ptr, _stream
 
-__all__ = ["Mimi"]
+__all__ = ["Mimi", "MimiEncodeStream"]
 
 
 class _NativeMimi:
@@ -234,6 +234,24 @@ class Mimi(Codec):
             )
         return out
 
+    # ---- streaming encode ------------------------------------------------------------------------
+    def encode_stream(self, batch_size: int, device=None) -> "MimiEncodeStream":
+        """A stateful signal -> tokens encoder for `batch_size` independent streams on `device` (default: the current cuda
+        device).  Feed it with `push`; every push returns the tokens of the frames it completed (include/audiocodecs_amd.h
+        ac_mimi_stream_*)."""
+        if self.mode == "decode":
+            raise ValueError("encode_stream needs the encoder: this Mimi was built with mode=\"decode\"")
+        if self.sample_rate != self.config.sampling_rate:
+            raise ValueError(
+                f"encode_stream runs at the codec's own rate ({self.config.sampling_rate} Hz) only: streaming resampling is not "
+                f"supported (sample_rate={self.sample_rate})"
+            )
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f"`batch_size` ({batch_size!r}) must be a positive int")
+        self._check_num_codebooks()
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return MimiEncodeStream(self, self._native_for(torch.empty(0, device=dev)), batch_size)
+
     # ---- measurement hook used by bench.py ------------------------------------------------------
     def profile_kernels(self, fn):
         nat = self._any_native()
@@ -245,3 +263,93 @@ class Mimi(Codec):
             n = nat.lib.ac_profile_end(nat.h, buf, 256)
         _native.check(n, nat.h, "ac_profile_end")
         return [(buf[i].name.decode(), buf[i].launches, buf[i].total_ms, buf[i].flops, buf[i].bytes) for i in range(n)]
+
+
+class MimiEncodeStream:
+    """Streaming Mimi encode of `batch_size` streams (Mimi.encode_stream).  `push(sig)` takes [B, L] fp32 samples on the codec's
+    device, any L >= 0, and returns the int64 tokens [B, n, K] of the n frames completed so far (n may be 0); a partial frame
+    waits here until a later push completes it (`pending` samples, always below hop).  The tokens of a stream do not depend on
+    how its signal was split into pushes, nor on the other streams.  The stream state and the workspace are device tensors owned
+    by this object."""
+
+    MAX_POSITIONS = 1 << 24     # transformer positions per stream (fp32 RoPE angle)
+
+    def __init__(self, codec: Mimi, nat: _NativeMimi, batch_size: int):
+        self.codec = codec
+        self._nat = nat
+        self.batch_size = B = batch_size
+        self.num_codebooks = codec.num_codebooks
+        self.hop = codec.config.hop_length
+        self.device = nat.device
+        nbytes = nat.lib.ac_mimi_stream_state_bytes(nat.h, B)
+        if nbytes == 0:
+            raise _native.NativeError("ac_mimi_stream_state_bytes returned 0")
+        self._state_buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self._state_buf.data_ptr()) % 256
+        self._state = self._state_buf[off:off + nbytes]
+        self._ws = None
+        self._pending = torch.empty(B, 0, dtype=torch.float32, device=self.device)
+        self._frames = [0] * B
+        self.reset()
+
+    @property
+    def pending(self) -> int:
+        return int(self._pending.shape[1])
+
+    def _call(self, rc, what):
+        _native.check(rc, self._nat.h, what)
+
+    @torch.no_grad()
+    def reset(self, streams=None) -> None:
+        """Start all streams afresh (dropping a pending partial frame), or only the listed slots (not while a partial frame is
+        pending: its samples belong to every slot)."""
+        nat, B = self._nat, self.batch_size
+        mask = None
+        if streams is not None:
+            idx = [streams] if isinstance(streams, int) else list(streams)
+            if any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < B for i in idx):
+                raise ValueError(f"`streams` ({streams!r}) must list slots in [0, {B})")
+            if self.pending:
+                raise ValueError(f"cannot reset single streams while {self.pending} samples of a partial frame are pending")
+            m = torch.zeros(B, dtype=torch.uint8)
+            m[idx] = 1
+            mask = m.to(self.device)
+            for i in idx:
+                self._frames[i] = 0
+        else:
+            self._pending = self._pending[:, :0]
+            self._frames = [0] * B
+        with torch.cuda.device(self.device):
+            self._call(nat.lib.ac_mimi_stream_reset(nat.h, _ptr(self._state), self._state.numel(), B, _ptr(mask), _stream()),
+                       "ac_mimi_stream_reset")
+
+    @torch.no_grad()
+    def push(self, sig: torch.Tensor) -> torch.Tensor:
+        B, hop, K = self.batch_size, self.hop, self.num_codebooks
+        if not isinstance(sig, torch.Tensor) or sig.dim() != 2 or sig.shape[0] != B:
+            raise ValueError(f"push expects a [{B}, L] tensor, got {tuple(sig.shape) if isinstance(sig, torch.Tensor) else type(sig)}")
+        if sig.dtype != torch.float32:
+            raise ValueError(f"push expects float32 samples, got {sig.dtype}")
+        if sig.device != self.device:
+            raise ValueError(f"push expects samples on {self.device}, got {sig.device}")
+        total = self.pending + sig.shape[1]
+        n = total // hop
+        if n == 0:
+            self._pending = torch.cat([self._pending, sig], 1) if sig.shape[1] else self._pending
+            return torch.empty(B, 0, K, dtype=torch.int64, device=self.device)
+        if 2 * (max(self._frames) + n) > self.MAX_POSITIONS:
+            raise ValueError(f"a stream would pass {self.MAX_POSITIONS} transformer positions: reset it first")
+        whole = torch.cat([self._pending, sig], 1) if self.pending else sig
+        chunk = whole[:, : n * hop].contiguous()
+        nat = self._nat
+        toks = torch.empty(B, n, K, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            need = nat.lib.ac_mimi_stream_workspace_bytes(nat.h, B, n)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            self._call(nat.lib.ac_mimi_stream_encode(nat.h, _ptr(self._state), self._state.numel(), _ptr(chunk), B, n, K, _ptr(toks),
+                                                     _ptr(self._ws), self._ws.numel(), _stream()), "ac_mimi_stream_encode")
+        self._pending = whole[:, n * hop:].clone()
+        self._frames = [f + n for f in self._frames]
+        return toks

@@ -290,6 +290,22 @@ int ac_quantize_ws(ac_handle* h, const float* feats_dev, int B, int N, int K, in
 int ac_dequantize_ws(ac_handle* h, const int64_t* toks_dev, int B, int N, int K, float* qfeats_dev,
                      void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Streaming Mimi encode: B streams, F whole frames (F * hop samples) per stream and push; tokens [B,F,K] in ac_encode's layout.
+ * The caller owns the stream state as device memory (ac_mimi_stream_state_bytes(h, B) bytes, 256-byte aligned), as it owns
+ * workspaces: per stream the padding cache of every causal conv of the encoder and of the down-sampler, a K/V ring of the last
+ * sliding_window - 1 positions per transformer layer, the absolute position and a "fresh" flag (DESIGN.md "Streaming Mimi encode").
+ * ac_mimi_stream_reset marks the streams of reset_mask_dev [B] (NULL: all) fresh at position 0; the rings are not cleared (entries
+ * from before a reset are masked by position).  A state must be reset on the handle, for the B it is used with, before its first
+ * ac_mimi_stream_encode, and its first reset takes no mask.  Returns AC_EINVAL for a non-Mimi handle, a state this handle never
+ * reset or reset for another B (the handle knows the states it reset by their address: memory reused at a reset state's address
+ * passes as that state), and AC_ENOMEM for a state or workspace (ac_mimi_stream_workspace_bytes(h, B, F)) that is too
+ * small; the handle stays usable.  Positions run up to 2^24 (the fp32 RoPE angle); no entry point allocates or synchronises. */
+size_t ac_mimi_stream_state_bytes(const ac_handle* h, int B);
+int ac_mimi_stream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, const uint8_t* reset_mask_dev, void* stream);
+size_t ac_mimi_stream_workspace_bytes(const ac_handle* h, int B, int F);
+int ac_mimi_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, const float* sig_dev, int B, int F, int K,
+                          int64_t* toks_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Copy the first K codebooks to embs_dev [K, codebook_size, ac_codebook_dim] fp32 (encodec.py:74-79;
  * mimi.py:52-62 `latent=True`). */
 int ac_embs(ac_handle* h, int K, float* embs_dev, void* stream);
