@@ -15,6 +15,8 @@ inside the timed step.  Rank 0 prints ONE JSON line (contract in the task statem
                   the dense fp16 MFMA peak (2.5 PF) for the split-operand tap-GEMM (3 fp16 partial products per fp32
                   product, split16.h; --precision fp32_exact: the exact-product kernels, bounded by the 157.3 TF fp32 MFMA
                   peak) or HBM (8 TB/s)
+A plain run stops there: set-up, warm-ups, the timed steps, --dump-outputs, the line.  Everything else the benchmark measures
+runs only with --full:
   cpu_baseline -- the CPU oracle (torch-CPU restatement of the reference) timed on this host's
                   cores on a bounded sample of the same workload.  Baseline only.
 and, at N = 1, outside the timed region (all skipped by --no-parity):
@@ -84,7 +86,7 @@ def cpu_baseline(codec_name, cfg, sd, sig_cpu, ncb):
     Threads: section 3 says all physical cores of the GPU host -- that run is made and reported (`all_physical_cores`), but
     torch's CPU convolutions do not scale to every core of a 2-socket host on a few clips, so a short scan (1 clip x 2 s per
     candidate) also picks the fastest thread count and `value` / `cores` are that faster configuration's.  Both are printed.
-    The sample is bounded (DAC: 1 clip, ~100 GMAC per audio-second) so that the default bench.py run finishes in minutes."""
+    The sample is bounded (DAC: 1 clip, ~100 GMAC per audio-second) so that a `bench.py --full` run finishes in minutes."""
     if codec_name == "mimi":
         from oracle import mimi_oracle as O
         W = O.cast_weights(sd)
@@ -525,7 +527,8 @@ def timed_steps(step, fence, steps, warmup, profile):
     """The contract's timed region: `warmup` untimed steps, then EXACTLY `steps` steps bracketed by fence() (barrier + device
     synchronise) on both sides -- once with the library's per-kernel events armed (`profile(fn)` returns their statistics: the
     roofline figures) and once more without them: the run `value` comes from.  Returns (dt with events, dt plain, statistics).
-    Every rank runs this; nothing here is rank-conditional."""
+    Both passes belong to every run, plain or --full: the plain pass is timed after the events pass as it always has been, and
+    tools/collect_traffic.py counts on this shape.  Every rank runs this; nothing here is rank-conditional."""
     for _ in range(warmup):
         step()
     fence()
@@ -655,7 +658,8 @@ def run(args, codec, cfg, sd, sig, sig_cpu, rank, world, dist, device):
         if args.dump_outputs:   # before any untimed extra runs the codec again
             out["dumped_outputs"] = dump_outputs(args.dump_outputs, last)
         last.clear()
-        extras = not args.no_parity and device.type == "cuda"
+        # a plain run ends here; everything below measures something besides the headline and runs only with --full
+        extras = args.full and not args.no_parity and device.type == "cuda"
         with torch.no_grad():
             if extras and args.codec == "encodec":
                 # a speech-like input beside the noise batch (amplitude-modulated multi-sines of tests/golden_cases.py
@@ -694,7 +698,7 @@ def run(args, codec, cfg, sd, sig, sig_cpu, rank, world, dist, device):
                     out["latency"] = latency_regime(codec, cfg)
                 except Exception as e:
                     out["latency"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline and sd is not None:
+        if world == 1 and args.full and not args.no_cpu_baseline and sd is not None:
             out["cpu_baseline"] = cpu_baseline(args.codec, cfg, sd, sig_cpu, ncb)
         if world == 1 and extras and not exact and not args.no_exact:
             # the split16 figure always travels with its exact-product twin: the same step with every product an IEEE fp32 product
@@ -778,11 +782,14 @@ def parse_args(argv=None):
                          "quoted for); fp32_exact = every product an IEEE fp32 product")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="nccl = RCCL on the GPUs (the measurement); gloo = tests only: the same launch + run() flow on CPU with a stub codec")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity gates and every other untimed extra (profiling passes: keeps the kernel trace to the timed workload)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE.json configs 3-5 (DAC, Mimi, WavTokenizer) that travel in the same JSON line")
-    ap.add_argument("--no-exact", action="store_true", help="skip the exact-fp32-product twin of the headline figure")
-    ap.add_argument("--no-latency", action="store_true", help="skip the B = 1 / B = 8 latency table (the reference's own measurement regime)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the CPU baseline, the parity gates, the speech-like input, the shader clock, the "
+                         "exact-fp32-product twin, the other configs and the latency table (the --no-* options below drop single ones)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity gates and every other untimed extra")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short runs of BASELINE.json configs 3-5 (DAC, Mimi, WavTokenizer) that travel in the same JSON line")
+    ap.add_argument("--no-exact", action="store_true", help="with --full: skip the exact-fp32-product twin of the headline figure")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the B = 1 / B = 8 latency table (the reference's own measurement regime)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0: tokens and decoded waveform) as "
                          "DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed, seeded sample of a larger array)")

@@ -5,7 +5,7 @@ T=${1:-r5w}
 O=gpurun_out/$T
 mkdir -p $O
 python -m pytest tests -m gpu -q -x > $O/pytest.log 2>&1; echo "pytest rc $?"; grep -E "passed|failed" $O/pytest.log | tail -2
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-400 $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-400 $O/bench.json
 cp gpurun_out/parity_report.json $O/parity_report.json 2>/dev/null
 for n in encodec wavtokenizer mimi dac; do
   case $n in encodec) b=64;; wavtokenizer) b=64;; mimi) b=128;; dac) b=39;; esac
