@@ -43,6 +43,14 @@ def pair(checkpoints):
     return fused, sep, cfg, sd
 
 
+def oracle_tokens(cfg, sd, case, sig, toks, length=None):
+    """The fp64-margin policy (test_gpu_parity.py) against the CPU oracle on the same inputs."""
+    from oracle import encodec_oracle as O
+    from test_round6_kernels_gpu import oracle_token_check
+
+    oracle_token_check(O, cfg, O.fold_weight_norm(sd), O.fold_weight_norm(sd, torch.float64), "encodec", case, sig, toks, length)
+
+
 def kernel_names(codec, fn):
     return {s[0] for s in codec.profile_kernels(fn)}
 
@@ -71,6 +79,7 @@ def test_encoder_front_matches_separate_kernels(pair, T):
     assert float((a - b).abs().max()) < 2e-5 * max(1.0, scale), (T, float((a - b).abs().max()), scale)
     ta, tb = fused.sig_to_toks(sig), sep.sig_to_toks(sig)
     assert float((ta == tb).float().mean()) > 0.995     # two fp32-faithful evaluations: only fp32-level near-ties may differ
+    oracle_tokens(cfg, sd, f"fused_front_T{T}", sig, ta)   # ... and the fused path against the oracle by the fp64-margin policy
 
 
 @pytest.mark.parametrize("N", [1, 2, 3, 7, 15, 16, 17, 75])
@@ -92,6 +101,7 @@ def test_ragged_length_mask_inside_the_fused_front(pair):
     length = torch.tensor([1.0, 0.7, 0.31, 0.003], device="cuda")
     a, b = fused.sig_to_toks(sig, length), sep.sig_to_toks(sig, length)
     assert float((a == b).float().mean()) > 0.995
+    oracle_tokens(cfg, sd, "fused_front_ragged_T4803", sig, a, length)
     masked = sig.clone()
     for i, l in enumerate(length.tolist()):
         masked[i, int(np.ceil(np.float32(T) * np.float32(l))):] = 0     # t >= T * length (fp32 product, as the kernel compares)

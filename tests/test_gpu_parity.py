@@ -282,8 +282,8 @@ FULL_DEC_TAPS = ["dec0", "dec1", "dec3", "dec4", "dec6", "dec7", "dec9", "dec10"
 
 
 def test_every_module_output_full_config_production_kernels(codecs, checkpoints):
-    """FULL architecture through the production kernels (stem, rb_fused6<32/64>, rb128_fused6, thin_conv6, tap_gemm6,
-    lstm_persist6, head): arming the capture hook does not change kernel selection; every module output of a 1 s clip
+    """FULL architecture through the production kernels (enc_stream, rb_stream6, rb_stream128m, the tap-GEMMs, the persistent
+    LSTM, dec_stream): arming the capture hook does not change kernel selection; every module output of a 1 s clip
     against the oracle's taps (the oracle is pinned to the reference's hooks on the tiny config and to its end-to-end
     outputs on this one).  A localized error shows up at its layer, not as a vague feature RMS."""
     from oracle import encodec_oracle as O

@@ -8,9 +8,21 @@ covered where their round-3 forms were (tests/test_fused_chains_gpu.py, the tap 
 import pytest
 import torch
 
+import parity_record
 from golden_cases import noise
+from test_oracle_golden import TAU
 
 pytestmark = pytest.mark.gpu
+
+
+def oracle_token_check(O, cfg, W, W64, codec_name, case, sig, toks, length=None):
+    """The fp64-margin policy against the CPU oracle on the inputs of a kernel-to-kernel comparison: the agreement rates asserted beside
+    it only say how far two kernels drift from each other."""
+    with torch.no_grad():
+        otoks = O.sig_to_toks(cfg, W, sig.cpu(), None if length is None else length.cpu())
+        _, m64 = O.sig_to_toks(cfg, W64, sig.cpu().double(), None if length is None else length.cpu().double(), 8, True)
+    mism, bad, excused = parity_record.tokens(codec_name, case, toks.cpu().numpy(), otoks.numpy(), m64.numpy(), TAU)
+    assert bad == 0 and mism <= excused, (case, mism, bad, excused)
 
 
 def _kernels(codec, fn):
@@ -49,6 +61,12 @@ def test_mimi_stem_and_head_folds_match_the_separate_kernels(B, T):
     scale = float(f0.abs().max())
     assert float((feats - f0).abs().max()) < 5e-5 * max(1.0, scale), (float((feats - f0).abs().max()), scale)
     assert float((toks == t0).float().mean()) > 0.99
+    from audiocodecs_amd import checkpoint
+    from audiocodecs_amd.config import MIMI_24KHZ
+    from oracle import mimi_oracle as O
+
+    sd = checkpoint.synthetic_mimi_state_dict(MIMI_24KHZ, seed=0)
+    oracle_token_check(O, MIMI_24KHZ, O.cast_weights(sd), O.cast_weights(sd, torch.float64), "mimi", f"round6_folds_B{B}_T{T}", sig, toks)
     assert float((wav - w0).abs().max()) <= 2e-5 * max(float(w0.abs().max()), 1e-3)
 
 
@@ -74,4 +92,7 @@ def test_rb_stream6_matches_rb_fused6_on_the_encodec_path(checkpoints, T):
         debug_set(codec, "rb_stream", 1)
     assert float((f1 - f0).abs().max()) < 2e-5 * max(1.0, float(f0.abs().max()))
     assert float((t1 == t0).float().mean()) > 0.995
+    from oracle import encodec_oracle as O
+
+    oracle_token_check(O, cfg, O.fold_weight_norm(sd), O.fold_weight_norm(sd, torch.float64), "encodec", f"round6_rb_stream6_T{T}", sig, t1)
     assert float((w1 - w0).abs().max()) <= 2e-5 * max(float(w0.abs().max()), 1e-3)
