@@ -2,7 +2,7 @@
 //   core.hip        the shared machinery (weight packing, split16 pools, tap-GEMM dispatch (its kernel choice: tap_route.h), fused-block / LSTM / codebook launchers,
 //                   workspace planning) and the EnCodec encoder / decoder; owns every kernel the codecs share
 //   mimi_path.hip, dac_path.hip, wavtok_path.hip   one codec each: plan, finalize, forward passes, its own kernels, its ac_*_create
-//   mimi_stream.hip streaming Mimi encode: the stream state, one push's launch sequence, its kernels and its ac_mimi_stream_* entry points
+//   mimi_stream.hip streaming Mimi encode and decode: the stream states, one push's launch sequence, its kernels and the ac_mimi_stream_* entry points
 //   ac_api.hip      the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
@@ -202,6 +202,7 @@ struct ac_handle {
         int dac_unit = 1;           // AC_DAC_UNIT=0       : DAC's 96-channel residual units as two tap-GEMM launches instead of dac_unit6_kernel
         int mimi_tail = 1;          // AC_MIMI_TAIL=0      : Mimi's last residual block and the final conv as two kernels (rb_fused6<64,false> + head4)
         int head_seq = 0;           // AC_HEAD_SEQ=1       : the one-thread-per-sample head kernel (A/B against head4_kernel)
+        int mstream_skinny = -1;    // AC_MSTREAM_SKINNY=-1|0|1: the linear layers of a streaming-decode push through mstream_linear_kernel by rows per launch (default) / never (tap-GEMM) / wherever the shape allows
     } dev;
     bool fuse_chains = true;        // AC_FUSE=0 at ac_finalize: the layers of the fused chains as separate kernels (A/B runs, cross-check tests)
     // test hook: copy every layer output (standard [B][L][C] layout) into a caller buffer
@@ -219,6 +220,7 @@ struct ac_handle {
                                     // (false: split16.h -- fp32-fidelity arithmetic of the matrix kernels, two fp16 planes, 3 products)
     std::map<size_t, size_t> winv_of;   // split16 images: float offset of a packed fp32 matrix -> offset of its per-row 2^-s
     std::map<const void*, int> mimi_streams;   // mimi_stream.hip: state buffers ac_mimi_stream_reset prepared on this handle -> their B
+    std::map<const void*, int> mimi_dstreams;  //   the same for decode states (ac_mimi_stream_decode_reset); an address is in at most one of the two
     // amax slots (split16.h): [slot][amax_B] words, handed out in launch order, cleared at the start of every pass
     unsigned* amax_buf = nullptr;
     int amax_B = 0, amax_next = 0;

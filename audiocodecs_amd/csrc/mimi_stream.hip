@@ -4,6 +4,13 @@
 // attention reads the K / V ring of the previous sliding_window - 1 positions (mstream_attn_kernel).  The fused batch-only blocks
 // (rb_stream6m with the folded stem, rb_stream128m, rb_fused6) assume zero history: a push goes through the per-conv tap-GEMMs.
 // The caller owns the state and the workspace; no entry point here allocates or synchronises.
+//
+// Streaming Mimi decode (ac_mimi_stream_decode*; DESIGN.md "Streaming Mimi decode") is the mirror image: a push of F token frames runs
+// the batch decoder's layers on [history | chunk] -- the up-sampler's previous input row, the decoder transformer's K / V rings
+// (positions advance resample_stride per frame), the first conv's k - 1 rows, each transposed conv's previous input row (with
+// k = 2 stride it is convtr_fwd's 2-tap row conv, its left zero row replaced by the cached one), each residual block's k3 history
+// and the head conv's.  A decode state has its own layout and magic and is registered separately on the handle.  The transformer's
+// linear layers of a push with few rows go through mstream_linear_kernel (mimi_stream.h) instead of the tap-GEMM.
 #include "core.h"
 #include "mimi_stream.h"
 
@@ -45,6 +52,32 @@ static MStreamLayout mstream_layout(const ac_handle* h, int B) {
     return L;
 }
 
+// decode state: the caches in decoder order -- up-sampler input, first conv, (transposed conv input, block k3) per ratio, head conv
+static MStreamLayout mdstream_layout(const ac_handle* h, int B) {
+    const ac_mimi_config& c = h->mcfg;
+    MStreamLayout L;
+    size_t off = align_up(sizeof(MStreamHeader), 256);
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    L.pos = take((size_t)B * 8);
+    L.fresh = take((size_t)B * 4);
+    auto conv = [&](int P, int C) { L.conv.push_back(take((size_t)B * std::max(P, 1) * C * 4)); L.conv_P.push_back(P); L.conv_C.push_back(C); };
+    conv(1, c.hidden_size);
+    conv(c.kernel_size - 1, c.hidden_size);
+    int ch = h->mimi.D;
+    for (int i = 0; i < c.num_ratios; ++i) {
+        conv(1, ch);
+        ch /= 2;
+        conv(c.residual_kernel_size - 1, ch);
+    }
+    conv(c.last_kernel_size - 1, ch);
+    L.R = c.sliding_window - 1;
+    L.A = c.num_attention_heads * c.head_dim;
+    L.ring = off;
+    off += (size_t)c.num_hidden_layers * 2 * align_up((size_t)B * L.R * L.A * 4, 256);
+    L.total = off;
+    return L;
+}
+
 static unsigned long long mstream_fingerprint(const ac_mimi_config& c) {
     ac_mimi_config k = c;
     k.device = 0;
@@ -57,13 +90,14 @@ static unsigned long long mstream_fingerprint(const ac_mimi_config& c) {
 static unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 65536); }
 
 // [cache | x] -> staged (a fresh activation buffer of B * (P + L) * C floats); x's last P rows -> cache
+// (`any_L`: a chunk shorter than the history is staged in two launches -- mimi_stream.h mstream_stage_ro_kernel; the encoder never has one)
 static int mstream_stage(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, int l, const Act& x, int B, float* staged,
-                         size_t cap, bool replicate) {
+                         size_t cap, bool replicate, bool any_L = false) {
     MStreamStageParams p{};
     p.P = Ls.conv_P[l];
     p.C = Ls.conv_C[l];
     if (x.C != p.C) return fail(h, AC_EINVAL, "stream stage %d: %d channels, cache holds %d", l, x.C, p.C);
-    if (x.L < p.P) return fail(h, AC_EINVAL, "stream stage %d: %d rows per push, fewer than the %d history rows", l, x.L, p.P);
+    if (x.L < p.P && !any_L) return fail(h, AC_EINVAL, "stream stage %d: %d rows per push, fewer than the %d history rows", l, x.L, p.P);
     if ((size_t)B * (p.P + x.L) * p.C > cap) return fail(h, AC_ENOMEM, "stream stage %d exceeds its workspace buffer", l);
     p.cache = reinterpret_cast<float*>(state + Ls.conv[l]);
     p.x = x.p;
@@ -75,6 +109,18 @@ static int mstream_stage(ac_handle* h, hipStream_t st, char* state, const MStrea
     p.L = x.L;
     p.replicate = replicate;
     const long long n = (long long)B * (p.P + x.L) * p.C;
+    if (x.L < p.P) {
+        {
+            ProfScope ps(h, st, "mstream_stage_ro_kernel", 0.0, 8.0 * n);
+            hipLaunchKernelGGL(mstream_stage_ro_kernel, dim3(grid_for(n)), dim3(256), 0, st, p);
+            HIPCHK(h, hipGetLastError());
+        }
+        const long long nc = (long long)B * p.P * p.C;
+        ProfScope ps(h, st, "mstream_cache_tail_kernel", 0.0, 8.0 * nc);
+        hipLaunchKernelGGL(mstream_cache_tail_kernel, dim3(grid_for(nc)), dim3(256), 0, st, p);
+        HIPCHK(h, hipGetLastError());
+        return AC_OK;
+    }
     ProfScope ps(h, st, "mstream_stage_kernel", 0.0, 8.0 * n);
     hipLaunchKernelGGL(mstream_stage_kernel, dim3(grid_for(n)), dim3(256), 0, st, p);
     HIPCHK(h, hipGetLastError());
@@ -120,8 +166,53 @@ static void rope_inv(const ac_handle* h, float* inv) {   // mimi_finalize's inv_
     for (int j = 0; j < c.head_dim / 2; ++j) inv[j] = 1.0f / std::pow(c.rope_theta, (float)(2 * j) / (float)c.head_dim);
 }
 
-// x [B*T][H] in place, as transformer_fwd, with the attention of mstream_attn_kernel
-static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, float* x, int B, int T, const MStreamScratch& s) {
+// Rows per launch (B * T) up to which the decode stream's linear layers take mstream_linear_kernel when the switch "mstream_skinny" is
+// on auto (-1).  Source: profiles/mimi_dstream_latency.jsonl (one MI355X, tools/mimi_stream_latency.py --direction decode
+// --linear-route ab, 200 pushes per route, median push latency tap-GEMM / skinny in ms): 2 rows 3.24 / 1.91, 8 rows 3.32 / 2.10,
+// 32 rows 3.76 / 2.53, 128 rows 4.33 / 3.48, 256 rows 5.34 / 5.12, 1280 rows 9.08 / 13.65.  128 is the largest measured point where the
+// skinny route wins by far more than the A/B's run-to-run spread (0.02 ms at 2 rows, p99 - median up to 0.3 ms); at 256 the two meet.
+constexpr int MSTREAM_SKINNY_AUTO_ROWS = 128;
+
+static bool mstream_skinny_ok(const PackedGemm& g, const float* x, int x_pitch, const float* y, int y_pitch, int K) {
+    return !g.has_bias && K == g.Ktot && K % 4 == 0 && (K / mstream_linear_ks(K)) % 4 == 0 && x_pitch % 4 == 0 && aligned16(x) && (g.w_off % 4) == 0 && y && y_pitch >= g.N;
+}
+
+template <int RB>
+static void mstream_linear_launch(hipStream_t st, const MStreamLinearParams& p) {
+    const dim3 grid((unsigned)p.N, (unsigned)cdiv(p.R, RB));
+    if (mstream_linear_ks(p.K) == 4) hipLaunchKernelGGL((mstream_linear_kernel<RB, 4>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((mstream_linear_kernel<RB, 1>), grid, dim3(64), 0, st, p);
+}
+
+// y[rows][N] = epi(x[rows][K] W^T) as mimi_linear computes it, on the plain fp32 matrix; shapes the kernel does not take go to mimi_linear
+static int mstream_linear(ac_handle* h, hipStream_t st, const PackedGemm& g, const float* x, long long rows, int K, float* y, int y_pitch, const Epi& epi, bool skinny) {
+    if (!skinny || rows > 65535LL * 8 || !mstream_skinny_ok(g, x, K, y, y_pitch, K)) return mimi_linear(h, st, g, x, rows, K, K, 0, y, y_pitch, epi);
+    MStreamLinearParams p{};
+    p.x = x;
+    p.w = h->blob + g.w_off;
+    p.y = y;
+    p.scale = epi.scale;
+    p.res = epi.res;
+    p.x_pitch = K;
+    p.y_pitch = y_pitch;
+    p.res_pitch = (int)epi.res_rs;
+    p.R = (int)rows;
+    p.N = g.N;
+    p.K = K;
+    p.gelu = epi.gelu;
+    if (epi.rowmax_out) *epi.rowmax_out = nullptr;
+    ProfScope ps(h, st, "mstream_linear_kernel", 2.0 * rows * g.N * K, 4.0 * ((double)g.N * K + (double)rows * (K + g.N)));
+    if (rows <= 2) mstream_linear_launch<2>(st, p);
+    else if (rows <= 4) mstream_linear_launch<4>(st, p);
+    else mstream_linear_launch<8>(st, p);
+    HIPCHK(h, hipGetLastError());
+    return AC_OK;
+}
+
+// x [B*T][H] in place, as transformer_fwd, with the attention of mstream_attn_kernel.  `skinny`: the linear layers through
+// mstream_linear (the decode stream's choice; the encode stream passes false and keeps the tap-GEMM route bit for bit)
+static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const std::vector<MimiTfLayer>& layers, bool skinny,
+                               float* x, int B, int T, const MStreamScratch& s) {
     const ac_mimi_config& c = h->mcfg;
     const int H = c.hidden_size, A = Ls.A, I = c.intermediate_size, R = Ls.R;
     const long long rows = (long long)B * T;
@@ -135,16 +226,16 @@ static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const 
     rp.A = A;
     rp.HD = c.head_dim;
     rope_inv(h, rp.inv);
-    for (size_t l = 0; l < h->mimi.enc_tf.size(); ++l) {
-        const MimiTfLayer& L = h->mimi.enc_tf[l];
+    for (size_t l = 0; l < layers.size(); ++l) {
+        const MimiTfLayer& L = layers[l];
         float* rk = reinterpret_cast<float*>(state + Ls.ring + (2 * l) * ring_bytes);
         float* rv = reinterpret_cast<float*>(state + Ls.ring + (2 * l + 1) * ring_bytes);
         const unsigned* ln_rows = nullptr;
-        int rc = layernorm_fwd(h, st, x, L.ln1_w, L.ln1_b, s.ln, rows, H, c.norm_eps, &ln_rows);
+        int rc = layernorm_fwd(h, st, x, L.ln1_w, L.ln1_b, s.ln, rows, H, c.norm_eps, skinny ? nullptr : &ln_rows);   // (row words: the split16 route's)
         if (rc) return rc;
         Epi eq;
         eq.rowmax_in = ln_rows;
-        if ((rc = mimi_linear(h, st, L.qkv, s.ln, rows, H, H, 0, s.qkv, 3 * A, eq))) return rc;
+        if ((rc = mstream_linear(h, st, L.qkv, s.ln, rows, H, s.qkv, 3 * A, eq, skinny))) return rc;
         {
             const long long n = rows * A;        // (q and k: 2 * heads * HD/2 pairs per row)
             ProfScope ps(h, st, "mstream_rope_kernel", 6.0 * n, 16.0 * n);
@@ -169,20 +260,20 @@ static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const 
         ea.scale = h->blob + L.sc_a;
         ea.res = x;
         ea.res_rs = H;
-        if ((rc = mimi_linear(h, st, L.o, s.att, rows, A, A, 0, x, H, ea))) return rc;
-        if ((rc = layernorm_fwd(h, st, x, L.ln2_w, L.ln2_b, s.ln, rows, H, c.norm_eps, &ln_rows))) return rc;
+        if ((rc = mstream_linear(h, st, L.o, s.att, rows, A, x, H, ea, skinny))) return rc;
+        if ((rc = layernorm_fwd(h, st, x, L.ln2_w, L.ln2_b, s.ln, rows, H, c.norm_eps, skinny ? nullptr : &ln_rows))) return rc;
         Epi eg;
         eg.gelu = 1;
         eg.rowmax_in = ln_rows;
         const unsigned* hid_rows = nullptr;
-        eg.rowmax_out = &hid_rows;
-        if ((rc = mimi_linear(h, st, L.fc1, s.ln, rows, H, H, 0, s.hid, I, eg))) return rc;
+        if (!skinny) eg.rowmax_out = &hid_rows;
+        if ((rc = mstream_linear(h, st, L.fc1, s.ln, rows, H, s.hid, I, eg, skinny))) return rc;
         Epi em;
         em.rowmax_in = hid_rows;
         em.scale = h->blob + L.sc_m;
         em.res = x;
         em.res_rs = H;
-        if ((rc = mimi_linear(h, st, L.fc2, s.hid, rows, I, I, 0, x, H, em))) return rc;
+        if ((rc = mstream_linear(h, st, L.fc2, s.hid, rows, I, x, H, em, skinny))) return rc;
     }
     return AC_OK;
 }
@@ -241,7 +332,7 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
     ws.give(stg);
     ++l;
     MStreamScratch s{ws.take(), ws.take(), ws.take(), ws.take()};
-    if ((rc = mstream_transformer(h, st, state, Ls, stream, B, T25, s))) return rc;
+    if ((rc = mstream_transformer(h, st, state, Ls, m.enc_tf, false, stream, B, T25, s))) return rc;
     ws.give(s.ln); ws.give(s.qkv); ws.give(s.att); ws.give(s.hid);
     stg = ws.take();
     const int H = c.hidden_size;
@@ -257,16 +348,104 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
     return AC_OK;
 }
 
+// one push: toks [B][F][K] -> sig [B][F*hop]; the decode state advances by F frames (mimi_decoder_fwd on [history | chunk])
+static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const long long* toks, int B, int F, int K, float* sig,
+                           WsPtrs& ws, size_t cap, bool skinny) {
+    const ac_mimi_config& c = h->mcfg;
+    const MimiPlan& m = h->mimi;
+    const int H = c.hidden_size, rs = c.resample_stride, T25 = F * rs;
+    int l = 0, rc;
+    float* qsum = ws.take();
+    float* qf = ws.take();
+    if ((rc = mimi_rvq_decode(h, st, toks, B * F, K, qsum, qf))) return rc;
+    ws.give(qsum);
+    // up-sampler: depthwise transposed conv (k = 2 stride) on [previous input row | chunk]
+    float* stg = ws.take();
+    if ((rc = mstream_stage(h, st, state, Ls, l, Act{qf, (long long)F * H, H, F, H}, B, stg, cap, false, true))) return rc;
+    ws.give(qf);
+    ++l;
+    float* stream = ws.take();
+    if ((size_t)B * T25 * H > cap) return fail(h, AC_ENOMEM, "stream up-sampler exceeds its workspace buffer");
+    {
+        MStreamUpsampleParams p{stg, h->blob + m.up_w, stream, B, F, H, rs};
+        const long long total = (long long)B * T25 * (H / 4);
+        ProfScope ps(h, st, "mstream_upsample_kernel", 4.0 * B * (double)T25 * H, 4.0 * B * (double)H * (F + 1 + T25));
+        hipLaunchKernelGGL(mstream_upsample_kernel, dim3(grid_for(total)), dim3(256), 0, st, p);
+        HIPCHK(h, hipGetLastError());
+    }
+    ws.give(stg);
+    MStreamScratch s{ws.take(), ws.take(), ws.take(), ws.take()};
+    if ((rc = mstream_transformer(h, st, state, Ls, m.dec_tf, skinny, stream, B, T25, s))) return rc;
+    ws.give(s.ln); ws.give(s.qkv); ws.give(s.att); ws.give(s.hid);
+    // first conv (k7) on [history | chunk]: a one-frame push brings fewer rows than the history holds
+    Act2 x, y;
+    stg = ws.take();
+    if ((rc = mstream_stage(h, st, state, Ls, l, Act{stream, (long long)T25 * H, H, T25, H}, B, stg, cap, false, true))) return rc;
+    ws.give(stream);
+    if ((rc = mstream_conv(h, st, m.dec_first, staged_act(stg, B, T25 + Ls.conv_P[l], H), c.kernel_size, 1, T25, Out{nullptr, ws.take()}, B, &x))) return rc;
+    ws.give(stg);
+    ++l;
+    for (int i = 0; i < c.num_ratios; ++i) {
+        const int ratio = c.upsampling_ratios[i], cin = m.dec_up[i].Ktot / 2, cup = m.dec_up[i].N / ratio, L = x.elu.L;
+        // transposed conv (k = 2 ratio): output row m = [x[m-1] | x[m]] Wp (convtr_fwd), x[-1] from the cache
+        stg = ws.take();
+        if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false, true))) return rc;
+        ws.give(x);
+        if ((rc = mstream_conv(h, st, m.dec_up[i], staged_act(stg, B, L + Ls.conv_P[l], cin), 2, 1, L, Out{ws.take(), ws.take()}, B, &y))) return rc;
+        ws.give(stg);
+        ++l;
+        const int Lu = L * ratio;                      // [B][L][ratio * cup] is [B][L * ratio][cup]
+        x.raw = Act{y.raw.p, (long long)Lu * cup, cup, Lu, cup, y.raw.amax, y.raw.amax_n};
+        x.elu = Act{y.elu.p, (long long)Lu * cup, cup, Lu, cup, y.elu.amax, y.elu.amax_n};
+        // residual block: x + conv_k1(ELU(conv_k3(ELU(x)))), the k3 conv on [history | ELU(x)]
+        const ResBlockPlan& rb = m.dec_rb[i];
+        stg = ws.take();
+        if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false, true))) return rc;
+        ws.give(x.elu.p);
+        float* hb = ws.take();
+        Act2 hv;
+        if ((rc = mstream_conv(h, st, rb.c3, staged_act(stg, B, Lu + Ls.conv_P[l], cup), c.residual_kernel_size, 1, Lu, Out{nullptr, hb}, B, &hv))) return rc;
+        ws.give(stg);
+        ++l;
+        Epi e;
+        e.res = x.raw.p;
+        e.res_bs = x.raw.bs;
+        e.res_rs = x.raw.ts;
+        const bool last = i == c.num_ratios - 1;       // the head conv reads ELU(y) only
+        if ((rc = mstream_conv(h, st, rb.fused, hv.elu, 1, 1, Lu, Out{last ? nullptr : ws.take(), ws.take()}, B, &y, e))) return rc;
+        ws.give(hb);
+        ws.give(x.raw.p);
+        x = y;
+    }
+    const int Ts = x.elu.L, Fh = c.num_filters;
+    stg = ws.take();
+    if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false, true))) return rc;
+    ws.give(x);
+    if ((rc = mstream_conv(h, st, m.dec_head, staged_act(stg, B, Ts + Ls.conv_P[l], Fh), c.last_kernel_size, 1, Ts, Out{sig, nullptr}, B, nullptr))) return rc;
+    ws.give(stg);
+    hipLaunchKernelGGL(mstream_advance_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
+                       reinterpret_cast<int*>(state + Ls.fresh), B, T25);
+    HIPCHK(h, hipGetLastError());
+    return AC_OK;
+}
+
+static Workspace mdstream_plan_ws(const ac_handle* h, int B, int F) {
+    // the batch plan for four frames more than the push: 4 * resample_stride >= kernel_size - 1 spare rows for the first conv's staged
+    // input (ac_mimi_create: kernel_size <= 8, resample_stride >= 1 -- two or more in every real model), and more than that at every later level
+    return mimi_plan_ws(h, B, 0, F + 4 + (h->mcfg.resample_stride == 1 ? 4 : 0), false);
+}
+
 static Workspace mstream_plan_ws(const ac_handle* h, int B, int F) {
     // the batch plan for one frame more than the push: every level gets hop / (its stride) >= k - stride spare rows for its history
     return mimi_plan_ws(h, B, (F + 1) * h->hop, 0, true);
 }
 
-static int mstream_check(ac_handle* h, int B) {
+static int mstream_check(ac_handle* h, int B, bool dec = false) {
     int rc = check_ready(h);
     if (rc) return rc;
     if (h->arch != ARCH_MIMI) return fail(h, AC_EINVAL, "ac_mimi_stream: not a Mimi handle");
-    if (!h->has_enc) return fail(h, AC_ESTATE, "ac_mimi_stream: the handle was loaded without encoder weights (mode=\"decode\")");
+    if (!dec && !h->has_enc) return fail(h, AC_ESTATE, "ac_mimi_stream: the handle was loaded without encoder weights (mode=\"decode\")");
+    if (dec && !h->has_dec) return fail(h, AC_ESTATE, "ac_mimi_stream_decode: the handle was loaded without decoder weights (mode=\"encode\")");
     if (B < 1) return fail(h, AC_EINVAL, "ac_mimi_stream: B=%d", B);
     if (h->mcfg.head_dim > MSTREAM_MAXHD) return fail(h, AC_EINVAL, "ac_mimi_stream: head_dim %d unsupported", h->mcfg.head_dim);
     return AC_OK;
@@ -304,6 +483,7 @@ int ac_mimi_stream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int 
                        reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh), reset_mask_dev, B);
     HIPCHK(h, hipGetLastError());
     h->mimi_streams[state_dev] = B;
+    h->mimi_dstreams.erase(state_dev);      // (the header just written makes it an encode state)
     return AC_OK;
 }
 
@@ -314,7 +494,8 @@ int ac_mimi_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, con
     if (!state_dev || !sig_dev || !toks_dev || F < 1) return fail(h, AC_EINVAL, "ac_mimi_stream_encode: bad argument (F=%d)", F);
     if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "ac_mimi_stream_encode: K=%d outside [1, %d]", K, h->mcfg.num_quantizers);
     auto it = h->mimi_streams.find(state_dev);
-    if (it == h->mimi_streams.end()) return fail(h, AC_EINVAL, "ac_mimi_stream_encode: the state was never reset on this handle");
+    if (it == h->mimi_streams.end())
+        return fail(h, AC_EINVAL, "ac_mimi_stream_encode: the state was never reset on this handle%s", h->mimi_dstreams.count(state_dev) ? " as an encode state (it is a decode state)" : "");
     if (it->second != B) return fail(h, AC_EINVAL, "ac_mimi_stream_encode: the state holds %d streams, B=%d", it->second, B);
     const MStreamLayout Ls = mstream_layout(h, B);
     if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "ac_mimi_stream_encode: state of %zu bytes, %zu needed", state_bytes, Ls.total);
@@ -333,6 +514,61 @@ int ac_mimi_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, con
     rc = mimi_linear(h, st, h->mimi.in_proj, feats, (long long)B * F, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
     if (rc) return rc;
     return mimi_rvq_encode(h, st, proj, B * F, K, reinterpret_cast<long long*>(toks_dev));
+}
+
+size_t ac_mimi_stream_decode_state_bytes(const ac_handle* h, int B) {
+    if (!h || B < 1 || h->arch != ARCH_MIMI) return 0;
+    return mdstream_layout(h, B).total;
+}
+
+size_t ac_mimi_stream_decode_workspace_bytes(const ac_handle* h, int B, int F) {
+    if (!h || B < 1 || F < 1 || h->arch != ARCH_MIMI) return 0;
+    return mdstream_plan_ws(h, B, F).total_bytes;
+}
+
+int ac_mimi_stream_decode_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, const uint8_t* reset_mask_dev, void* stream) {
+    int rc = mstream_check(h, B, true);
+    if (rc) return rc;
+    if (!state_dev) return fail(h, AC_EINVAL, "ac_mimi_stream_decode_reset: state is null");
+    const MStreamLayout Ls = mdstream_layout(h, B);
+    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "ac_mimi_stream_decode_reset: state of %zu bytes, %zu needed", state_bytes, Ls.total);
+    if ((reinterpret_cast<uintptr_t>(state_dev) & 255) != 0) return fail(h, AC_EINVAL, "ac_mimi_stream_decode_reset: state must be 256-byte aligned");
+    auto it = h->mimi_dstreams.find(state_dev);
+    if (reset_mask_dev && (it == h->mimi_dstreams.end() || it->second != B))
+        return fail(h, AC_EINVAL, "ac_mimi_stream_decode_reset: a masked reset needs a decode state this handle reset for B=%d before", B);
+    char* s = static_cast<char*>(state_dev);
+    MStreamHeader hd{MDSTREAM_MAGIC, 1u, mstream_fingerprint(h->mcfg), B, 0};
+    hipLaunchKernelGGL(mstream_reset_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<MStreamHeader*>(s), hd,
+                       reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh), reset_mask_dev, B);
+    HIPCHK(h, hipGetLastError());
+    h->mimi_dstreams[state_dev] = B;
+    h->mimi_streams.erase(state_dev);       // (the header just written makes it a decode state)
+    return AC_OK;
+}
+
+int ac_mimi_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K, float* sig_dev,
+                          void* ws, size_t ws_bytes, void* stream) {
+    int rc = mstream_check(h, B, true);
+    if (rc) return rc;
+    if (!state_dev || !sig_dev || !toks_dev || F < 1) return fail(h, AC_EINVAL, "ac_mimi_stream_decode: bad argument (F=%d)", F);
+    if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "ac_mimi_stream_decode: K=%d outside [1, %d]", K, h->mcfg.num_quantizers);
+    auto it = h->mimi_dstreams.find(state_dev);
+    if (it == h->mimi_dstreams.end())
+        return fail(h, AC_EINVAL, "ac_mimi_stream_decode: the state was never reset as a decode state on this handle%s",
+                    h->mimi_streams.count(state_dev) ? " (it is an encode state)" : "");
+    if (it->second != B) return fail(h, AC_EINVAL, "ac_mimi_stream_decode: the state holds %d streams, B=%d", it->second, B);
+    const MStreamLayout Ls = mdstream_layout(h, B);
+    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "ac_mimi_stream_decode: state of %zu bytes, %zu needed", state_bytes, Ls.total);
+    if ((long long)F * h->hop > 0x7fffffffLL / 64) return fail(h, AC_EINVAL, "ac_mimi_stream_decode: F=%d frames per push is too many", F);
+    const Workspace w = mdstream_plan_ws(h, B, F);
+    WsPtrs p;
+    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = amax_begin(h, st, B))) return rc;
+    const long long rows = (long long)B * F * h->mcfg.resample_stride;      // rows of one linear-layer launch
+    const int sw = h->dev.mstream_skinny;
+    const bool skinny = sw > 0 || (sw < 0 && rows <= MSTREAM_SKINNY_AUTO_ROWS);
+    return mstream_decoder(h, st, static_cast<char*>(state_dev), Ls, reinterpret_cast<const long long*>(toks_dev), B, F, K, sig_dev, p, w.act_floats, skinny);
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@ from .codec import Codec
 from .config import MIMI_24KHZ, MimiConfig
 from .encodec import _ptr, _stream
 
-__all__ = ["Mimi", "MimiEncodeStream"]
+__all__ = ["Mimi", "MimiEncodeStream", "MimiDecodeStream"]
 
 
 class _NativeMimi:
@@ -252,6 +252,24 @@ class Mimi(Codec):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         return MimiEncodeStream(self, self._native_for(torch.empty(0, device=dev)), batch_size)
 
+    # ---- streaming decode ------------------------------------------------------------------------
+    def decode_stream(self, batch_size: int, device=None) -> "MimiDecodeStream":
+        """A stateful tokens -> signal decoder for `batch_size` independent streams on `device` (default: the current cuda
+        device).  Feed it with `push`; every push returns the samples of the frames it was given (include/audiocodecs_amd.h
+        ac_mimi_stream_decode*)."""
+        if self.mode == "encode":
+            raise ValueError("decode_stream needs the decoder: this Mimi was built with mode=\"encode\"")
+        if self.sample_rate != self.config.sampling_rate:
+            raise ValueError(
+                f"decode_stream runs at the codec's own rate ({self.config.sampling_rate} Hz) only: streaming resampling is not "
+                f"supported (sample_rate={self.sample_rate})"
+            )
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f"`batch_size` ({batch_size!r}) must be a positive int")
+        self._check_num_codebooks()
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return MimiDecodeStream(self, self._native_for(torch.empty(0, device=dev)), batch_size)
+
     # ---- measurement hook used by bench.py ------------------------------------------------------
     def profile_kernels(self, fn):
         nat = self._any_native()
@@ -353,3 +371,81 @@ class MimiEncodeStream:
         self._pending = whole[:, n * hop:].clone()
         self._frames = [f + n for f in self._frames]
         return toks
+
+
+class MimiDecodeStream:
+    """Streaming Mimi decode of `batch_size` streams (Mimi.decode_stream).  `push(toks)` takes [B, F, K] int64 tokens on the codec's
+    device, K = the codec's `num_codebooks`, any F >= 0, and returns the [B, F * hop] fp32 samples of those frames at the codec's own
+    rate.  The samples of a stream are those `toks_to_sig` gives on the stream's whole token sequence, for any number of frames, and
+    do not depend on the other streams.  The stream state and the workspace are device tensors owned by this object."""
+
+    MAX_POSITIONS = 1 << 24     # transformer positions per stream (fp32 RoPE angle)
+
+    def __init__(self, codec: Mimi, nat: _NativeMimi, batch_size: int):
+        self.codec = codec
+        self._nat = nat
+        self.batch_size = B = batch_size
+        self.num_codebooks = codec.num_codebooks
+        self.hop = codec.config.hop_length
+        self._stride = codec.config.resample_stride
+        self.device = nat.device
+        nbytes = nat.lib.ac_mimi_stream_decode_state_bytes(nat.h, B)
+        if nbytes == 0:
+            raise _native.NativeError("ac_mimi_stream_decode_state_bytes returned 0")
+        self._state_buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self._state_buf.data_ptr()) % 256
+        self._state = self._state_buf[off:off + nbytes]
+        self._ws = None
+        self._frames = [0] * B
+        self.reset()
+
+    def _call(self, rc, what):
+        _native.check(rc, self._nat.h, what)
+
+    @torch.no_grad()
+    def reset(self, streams=None) -> None:
+        """Start all streams afresh, or only the listed slots."""
+        nat, B = self._nat, self.batch_size
+        mask = None
+        if streams is not None:
+            idx = [streams] if isinstance(streams, int) and not isinstance(streams, bool) else list(streams)
+            if any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < B for i in idx):
+                raise ValueError(f"`streams` ({streams!r}) must list slots in [0, {B})")
+            m = torch.zeros(B, dtype=torch.uint8)
+            m[idx] = 1
+            mask = m.to(self.device)
+        with torch.cuda.device(self.device):
+            self._call(nat.lib.ac_mimi_stream_decode_reset(nat.h, _ptr(self._state), self._state.numel(), B, _ptr(mask), _stream()),
+                       "ac_mimi_stream_decode_reset")
+        if streams is None:
+            self._frames = [0] * B
+        else:
+            for i in idx:
+                self._frames[i] = 0
+
+    @torch.no_grad()
+    def push(self, toks: torch.Tensor) -> torch.Tensor:
+        B, hop, K = self.batch_size, self.hop, self.num_codebooks
+        if not isinstance(toks, torch.Tensor) or toks.dim() != 3 or toks.shape[0] != B or toks.shape[2] != K:
+            raise ValueError(f"push expects a [{B}, F, {K}] tensor, got {tuple(toks.shape) if isinstance(toks, torch.Tensor) else type(toks)}")
+        if toks.dtype != torch.int64:
+            raise ValueError(f"push expects int64 tokens, got {toks.dtype}")
+        if toks.device != self.device:
+            raise ValueError(f"push expects tokens on {self.device}, got {toks.device}")
+        F = toks.shape[1]
+        if F == 0:
+            return torch.empty(B, 0, dtype=torch.float32, device=self.device)
+        if self._stride * (max(self._frames) + F) > self.MAX_POSITIONS:
+            raise ValueError(f"a stream would pass {self.MAX_POSITIONS} transformer positions: reset it first")
+        toks = toks.contiguous()
+        nat = self._nat
+        sig = torch.empty(B, F * hop, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            need = nat.lib.ac_mimi_stream_decode_workspace_bytes(nat.h, B, F)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            self._call(nat.lib.ac_mimi_stream_decode(nat.h, _ptr(self._state), self._state.numel(), _ptr(toks), B, F, K, _ptr(sig),
+                                                     _ptr(self._ws), self._ws.numel(), _stream()), "ac_mimi_stream_decode")
+        self._frames = [f + F for f in self._frames]
+        return sig

@@ -306,6 +306,25 @@ size_t ac_mimi_stream_workspace_bytes(const ac_handle* h, int B, int F);
 int ac_mimi_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, const float* sig_dev, int B, int F, int K,
                           int64_t* toks_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Streaming Mimi decode: B streams, F token frames per stream and push; toks_dev [B,F,K] in ac_decode's layout, sig_dev [B, F * hop]
+ * fp32.  Decoding a stream frame by frame gives what ac_decode gives on the whole token sequence (the decoder is causal), for any
+ * number of frames: positions are not bounded by ac_decode's RoPE table.  Same contract as the encode side: the caller owns the
+ * state (ac_mimi_stream_decode_state_bytes(h, B) bytes, 256-byte aligned) and the workspace
+ * (ac_mimi_stream_decode_workspace_bytes(h, B, F)); nothing allocates or synchronises.  Per stream the state holds the up-sampler's
+ * previous input row, a K/V ring per layer of the decoder transformer (positions advance resample_stride per frame), the padding
+ * cache of the first conv, of every transposed conv (its previous input row) and residual block, and of the head conv, the position
+ * and the "fresh" flag (DESIGN.md "Streaming Mimi decode").  A decode state is NOT an encode state: it has its own layout and header
+ * and the handle registers it as such -- an encode state passed to ac_mimi_stream_decode / _decode_reset (masked), or a decode state
+ * passed to ac_mimi_stream_encode, is AC_EINVAL; resetting a buffer as one kind ends its life as the other.  AC_ESTATE for a handle
+ * loaded without decoder weights; AC_EINVAL / AC_ENOMEM otherwise as for the encode side, decided on the host, and the handle and the
+ * state stay usable.  Token ids outside [0, codebook_size) behave as in ac_decode: the frame is NaN (and what follows it in that
+ * stream, through the state) and the NEXT entry point returns AC_EINVAL. */
+size_t ac_mimi_stream_decode_state_bytes(const ac_handle* h, int B);
+int ac_mimi_stream_decode_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, const uint8_t* reset_mask_dev, void* stream);
+size_t ac_mimi_stream_decode_workspace_bytes(const ac_handle* h, int B, int F);
+int ac_mimi_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K,
+                          float* sig_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Copy the first K codebooks to embs_dev [K, codebook_size, ac_codebook_dim] fp32 (encodec.py:74-79;
  * mimi.py:52-62 `latent=True`). */
 int ac_embs(ac_handle* h, int K, float* embs_dev, void* stream);
@@ -342,7 +361,8 @@ int ac_debug_capture(ac_handle* h, float* buf_dev, size_t cap_floats);
 /* Developer / test switches of a handle: A/B paths whose results are EQUIVALENT (bit-identical or fp32-faithful; named in the
  * parity tests): "tap_epi_staged", "tap_dil", "tap_stagger", "tap_pick", "tap8", "tap8_form", "tap8_spread", "rb_stream",
  * "rb128_stream", "chain_stream", "front_seg", "tail_seg", "front_ldspad", "lstm_fuse_in", "rvq_exact", "prof_detail", "head_seq", "attn_exact",
- * "dac_unit", "mimi_tail".  Their initial values come from the environment variables of the same meaning (AC_TAP_EPI, AC_TAP_DIL,
+ * "dac_unit", "mimi_tail", "mstream_skinny" (the linear layers of an ac_mimi_stream_decode push: 0 = tap-GEMM, 1 = the weight-streaming
+ * mstream_linear_kernel wherever the shape allows, -1 = by rows per launch).  Their initial values come from the environment variables of the same meaning (AC_TAP_EPI, AC_TAP_DIL,
  * ...), read ONCE, at ac_finalize; no compute entry point reads the environment.
  * "rb6_dbg" (timing modes with WRONG results) and "lstm_dbg" (fault injection, traces) exist in the DEVELOPER library only
  * (libaudiocodecs_amd_dev.so, built beside the product by csrc/build.sh with -DAC_DEVELOPER): the product library returns AC_EINVAL for
