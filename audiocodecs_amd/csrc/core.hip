@@ -996,11 +996,13 @@ int lstm_fwd(ac_handle* h, hipStream_t st, const LstmPlan& lp, const Act& x, con
                 q6.poison = poison;
                 q6.hseq0_local = ws.gin1;     // free on this path (the per-step kernels' layer-1 pre-activations)
                 HIPCHK(h, hipMemsetAsync(h->lp_ctl, 0, LP_CTL_WORDS * sizeof(unsigned), st));
-                // the exchange validates itself: every element of the h buffers starts as the "not yet written" pattern
+                // the exchange validates itself: every element of the h buffers starts as the "not yet written" pattern.  The two
+                // recurrent exchanges are rings that the kernel re-arms itself (LP16_RING): only the hand-over has a block per step
                 const size_t hbytes = (size_t)T * (size_t)q6.base.h_ts;
+                const size_t rbytes = (size_t)std::min(T, LP16_RING) * (size_t)q6.base.h_ts;
                 HIPCHK(h, hipMemsetAsync(ws.hseq0, 0xFF, hbytes, st));
-                HIPCHK(h, hipMemsetAsync(ws.hseq1, 0xFF, hbytes, st));
-                HIPCHK(h, hipMemsetAsync(ws.gin1, 0xFF, hbytes, st));
+                HIPCHK(h, hipMemsetAsync(ws.hseq1, 0xFF, rbytes, st));
+                HIPCHK(h, hipMemsetAsync(ws.gin1, 0xFF, rbytes, st));
                 void* args6[] = {&q6};
                 const void* kfn = fuse_in ? reinterpret_cast<const void*>(lstm_persist16_kernel<true>) : reinterpret_cast<const void*>(lstm_persist16_kernel<false>);
                 HIPCHK(h, hipLaunchCooperativeKernel(kfn, dim3(256), dim3(512), args6, 0, st));

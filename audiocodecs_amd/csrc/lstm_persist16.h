@@ -41,6 +41,19 @@ namespace ac {
 // memory system performs the loads.  One round trip instead of flag poll + dependent load; spins are bounded by the timeout word.
 constexpr int LP16_SLICE_BYTES = 2 * 16 * 16 * 2;    // 1024
 constexpr long long LP16_GROUP_BYTES = (long long)LP_SLICES * LP16_SLICE_BYTES;
+// The RECURRENT exchange of a layer (hseq0_local, hseq1: written and read inside one XCD) is a RING of LP16_RING time steps: step t lives
+// in slot t % LP16_RING, and the host fills only the ring before a launch (the cross-XCD hand-over hseq0 keeps one block per step: layer 0
+// runs any number of steps ahead of layer 1).  A slice re-arms its own block of step t - 2 with the "not yet written" pattern in step t,
+// behind the barrier that follows the validation of every peer's h[t-1]: a peer that has published h[t-1] has consumed h[t-2] (its waves
+// validated it in front of their own barrier of step t - 1 and never read it again).  The slot is written again in step t - 2 + LP16_RING.
+// A reader must not find the OLD block there: it reads that slot only when it has seen this slice's h[t-3+LP16_RING], published
+// >= one step behind h[t+1] -- and the re-arming stores are acknowledged by the XCD's L2 before this slice publishes h[t+1] (the memory
+// counter is in order: the wait for the recurrent operand of step t + 1, requested behind them, covers them).  Hence LP16_RING >= 4.
+#ifndef LP16_RING_N
+#define LP16_RING_N 8
+#endif
+constexpr int LP16_RING = LP16_RING_N;
+static_assert(LP16_RING >= 4 && (LP16_RING & (LP16_RING - 1)) == 0, "ring of the recurrent exchange: a power of two, >= 4 (see above)");
 
 struct LstmPersist16Params {
     LstmPersistParams base;     // hseq0 / hseq1 are byte buffers of fp16 plane blocks here; h_ts = bytes per time step
@@ -55,7 +68,7 @@ struct LstmPersist16Params {
     // share the accumulator, so their rows share the scale); amax slot of x (indexed by clip, fuse_in only)
     const float* winv;
     const unsigned* amax_x;
-    void* hseq0_local;          // layer 0's own copy of h0 (same layout as hseq0)
+    void* hseq0_local;          // layer 0's own copy of h0 (hseq0's block layout; a ring of LP16_RING steps, like hseq1 here)
 };
 
 #ifndef LP16_HEXP
@@ -169,6 +182,7 @@ __global__ __launch_bounds__(512) void lstm_persist16_kernel(const LstmPersist16
     char* h1b = reinterpret_cast<char*>(p.hseq1);
     char* hmine = layer ? h1b : reinterpret_cast<char*>(pp.hseq0_local);
     const long long goff = (long long)(p.group0 + g) * GROUP_BYTES;
+    auto rt = [](int t) { return t & (LP16_RING - 1); };      // ring slot of step t of the recurrent exchange (hmine)
 
     // gate threads: the first 256 threads own (clip ec, unit ej) of the slice, as in the 4-wave kernels
     const bool gate_thr = tid < 256;
@@ -284,7 +298,7 @@ __global__ __launch_bounds__(512) void lstm_persist16_kernel(const LstmPersist16
         for (int n = 0; n < 4; ++n) accP[n] = f32x4{0.f, 0.f, 0.f, 0.f};
         // NO request below sits under a condition: a register that is loaded on one path and carried on the other becomes a
         // copy at the join -- and the copy waits for the load (the loop latch then waited for every request of the step)
-        if constexpr (decltype(rec_tag)::value && !LATE) load_a(hmine, trec, arec);
+        if constexpr (decltype(rec_tag)::value && !LATE) load_a(hmine, rt(trec), arec);
         mac(a, wb, accP, 0, 1);
         mac(a, wb, accP, 1, 2);
 #pragma unroll
@@ -294,7 +308,7 @@ __global__ __launch_bounds__(512) void lstm_persist16_kernel(const LstmPersist16
         if constexpr (decltype(rec_tag)::value && LATE) {
             __builtin_amdgcn_sched_barrier(0);
             await_publish(trec);
-            load_a(hmine, trec, arec);
+            load_a(hmine, rt(trec), arec);
         }
         (void)t;
     };
@@ -349,7 +363,7 @@ __global__ __launch_bounds__(512) void lstm_persist16_kernel(const LstmPersist16
             // (arec: requested in the previous step's projection; incomplete, or never requested without a projection: poll)
             const bool first_ok = (layer == 1 || fuse0) && (valid(arec) || AC_DEV_MODE(p.dbg, 4));
             if (trc && !first_ok) trw[63] += 1;                    // developer trace: steps whose early request came back incomplete
-            if (!first_ok && !load_valid(hmine, t - 1, arec)) return false;
+            if (!first_ok && !load_valid(hmine, rt(t - 1), arec)) return false;
             LP16_TRC(1);
             if (layer == 0) mac(arec, wa, acc);
             else mac(arec, wb, acc);
@@ -402,12 +416,18 @@ __global__ __launch_bounds__(512) void lstm_persist16_kernel(const LstmPersist16
             _Float16 hh = (_Float16)h2;
             if (LP16_HEXP && fabsf((float)hh) >= 2.0f) hh = (_Float16)copysignf(1.9990234375f, h2);
             const _Float16 hl = (_Float16)(h2 - (float)hh);
-            char* dst = hmine + (long long)t * p.h_ts + goff + (long long)idx * SLICE_BYTES;
+            char* dst = hmine + (long long)rt(t) * p.h_ts + goff + (long long)idx * SLICE_BYTES;
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, SLICE_BYTES, 0x00020000);
             __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, hh), rs, hpos, 0, LP_SC0);
             __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, hl), rs, 512 + hpos, 0, LP_SC0);
             LP16_TRC(7);
             if (lane == 0) pubflag[wave] = (unsigned)t + 1u;    // (LATE waves: await_publish)
+            if (t >= 2) {   // re-arm this thread's element of step t - 2: every peer has consumed it (LP16_RING above)
+                char* old = hmine + (long long)rt(t - 2) * p.h_ts + goff + (long long)idx * SLICE_BYTES;
+                const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)old, 0, SLICE_BYTES, 0x00020000);
+                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)0xFFFFu, ro, hpos, 0, LP_SC0);
+                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)0xFFFFu, ro, 512 + hpos, 0, LP_SC0);
+            }
             if (layer == 0) {   // the copy layer 1 reads from the neighbouring XCD: kept for the batch store below
                 hist[t % LP16_BATCH][0][tid] = __builtin_bit_cast(unsigned short, hh);
                 hist[t % LP16_BATCH][1][tid] = __builtin_bit_cast(unsigned short, hl);
@@ -433,7 +453,7 @@ __global__ __launch_bounds__(512) void lstm_persist16_kernel(const LstmPersist16
             if (!ap_ok && !load_valid(h0b, t1, ap)) return false;   // layer 0 is steps ahead: normally complete
 #pragma unroll
             for (int n = 0; n < 4; ++n) accP[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (!LATE) load_a(hmine, t, arec);
+            if constexpr (!LATE) load_a(hmine, rt(t), arec);
             mac(ap, wa, accP, 0, 1);
             // cross-XCD / HBM round trips go BEHIND the recurrent request and have a whole step to arrive
             if constexpr (!LATE) skip_next = skip_row[(long long)t1 * D];
@@ -441,7 +461,7 @@ __global__ __launch_bounds__(512) void lstm_persist16_kernel(const LstmPersist16
             if constexpr (LATE) {
                 __builtin_amdgcn_sched_barrier(0);
                 await_publish(t);
-                load_a(hmine, t, arec);
+                load_a(hmine, rt(t), arec);
                 skip_next = skip_row[(long long)t1 * D];
             }
             load_a(h0b, t + 2 < p.T ? t + 2 : t1, ap);
