@@ -163,6 +163,14 @@ EXPORTS = {
     "ac_mimi_stream_decode_reset": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
     "ac_mimi_stream_decode_workspace_bytes": (_sz, [_vp, _i, _i]),
     "ac_mimi_stream_decode": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ac_encodec_stream_state_bytes": (_sz, [_vp, _i]),
+    "ac_encodec_stream_reset": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
+    "ac_encodec_stream_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "ac_encodec_stream_encode": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ac_encodec_stream_decode_state_bytes": (_sz, [_vp, _i]),
+    "ac_encodec_stream_decode_reset": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
+    "ac_encodec_stream_decode_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "ac_encodec_stream_decode": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ac_embs": (_i, [_vp, _i, _vp, _vp]),
     "ac_embs_projected": (_i, [_vp, _i, _vp, _vp]),
     "ac_resample": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -3,6 +3,8 @@
 //                   workspace planning) and the EnCodec encoder / decoder; owns every kernel the codecs share
 //   mimi_path.hip, dac_path.hip, wavtok_path.hip   one codec each: plan, finalize, forward passes, its own kernels, its ac_*_create
 //   mimi_stream.hip streaming Mimi encode and decode: the stream states, one push's launch sequence, its kernels and the ac_mimi_stream_* entry points
+//   encodec_stream.hip streaming EnCodec encode and decode: the stream states (conv histories, the LSTM's h and c), one push's launch sequence,
+//                   the stateful LSTM step kernel and the ac_encodec_stream_* entry points (stream_stage.h / stream_launch.h: what it shares with mimi_stream.hip)
 //   ac_api.hip      the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
@@ -221,6 +223,8 @@ struct ac_handle {
     std::map<size_t, size_t> winv_of;   // split16 images: float offset of a packed fp32 matrix -> offset of its per-row 2^-s
     std::map<const void*, int> mimi_streams;   // mimi_stream.hip: state buffers ac_mimi_stream_reset prepared on this handle -> their B
     std::map<const void*, int> mimi_dstreams;  //   the same for decode states (ac_mimi_stream_decode_reset); an address is in at most one of the two
+    struct EStreamReg { int B; bool fresh; };  // encodec_stream.hip: `fresh`: no push since the reset (the next one must bring the warm-up frames)
+    std::map<const void*, EStreamReg> encodec_streams, encodec_dstreams;   //   states ac_encodec_stream_reset / _decode_reset prepared on this handle
     // amax slots (split16.h): [slot][amax_B] words, handed out in launch order, cleared at the start of every pass
     unsigned* amax_buf = nullptr;
     int amax_B = 0, amax_next = 0;

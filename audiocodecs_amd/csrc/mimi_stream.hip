@@ -10,8 +10,9 @@
 // (positions advance resample_stride per frame), the first conv's k - 1 rows, each transposed conv's previous input row (with
 // k = 2 stride it is convtr_fwd's 2-tap row conv, its left zero row replaced by the cached one), each residual block's k3 history
 // and the head conv's.  A decode state has its own layout and magic and is registered separately on the handle.  The transformer's
-// linear layers of a push with few rows go through mstream_linear_kernel (mimi_stream.h) instead of the tap-GEMM.
+// linear layers of a push with few rows go through mstream_linear_kernel (stream_stage.h) instead of the tap-GEMM.
 #include "core.h"
+#include "stream_launch.h"
 #include "mimi_stream.h"
 
 namespace acimpl {
@@ -87,79 +88,16 @@ static unsigned long long mstream_fingerprint(const ac_mimi_config& c) {
     return f;
 }
 
-static unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 65536); }
-
-// [cache | x] -> staged (a fresh activation buffer of B * (P + L) * C floats); x's last P rows -> cache
-// (`any_L`: a chunk shorter than the history is staged in two launches -- mimi_stream.h mstream_stage_ro_kernel; the encoder never has one)
+// [cache | x] -> staged, x's last P rows -> cache (stream_launch.h), on cache `l` of the state
 static int mstream_stage(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, int l, const Act& x, int B, float* staged,
                          size_t cap, bool replicate, bool any_L = false) {
-    MStreamStageParams p{};
-    p.P = Ls.conv_P[l];
-    p.C = Ls.conv_C[l];
-    if (x.C != p.C) return fail(h, AC_EINVAL, "stream stage %d: %d channels, cache holds %d", l, x.C, p.C);
-    if (x.L < p.P && !any_L) return fail(h, AC_EINVAL, "stream stage %d: %d rows per push, fewer than the %d history rows", l, x.L, p.P);
-    if ((size_t)B * (p.P + x.L) * p.C > cap) return fail(h, AC_ENOMEM, "stream stage %d exceeds its workspace buffer", l);
-    p.cache = reinterpret_cast<float*>(state + Ls.conv[l]);
-    p.x = x.p;
-    p.bs = x.bs;
-    p.ts = x.ts;
-    p.y = staged;
-    p.fresh = reinterpret_cast<const int*>(state + Ls.fresh);
-    p.B = B;
-    p.L = x.L;
-    p.replicate = replicate;
-    const long long n = (long long)B * (p.P + x.L) * p.C;
-    if (x.L < p.P) {
-        {
-            ProfScope ps(h, st, "mstream_stage_ro_kernel", 0.0, 8.0 * n);
-            hipLaunchKernelGGL(mstream_stage_ro_kernel, dim3(grid_for(n)), dim3(256), 0, st, p);
-            HIPCHK(h, hipGetLastError());
-        }
-        const long long nc = (long long)B * p.P * p.C;
-        ProfScope ps(h, st, "mstream_cache_tail_kernel", 0.0, 8.0 * nc);
-        hipLaunchKernelGGL(mstream_cache_tail_kernel, dim3(grid_for(nc)), dim3(256), 0, st, p);
-        HIPCHK(h, hipGetLastError());
-        return AC_OK;
-    }
-    ProfScope ps(h, st, "mstream_stage_kernel", 0.0, 8.0 * n);
-    hipLaunchKernelGGL(mstream_stage_kernel, dim3(grid_for(n)), dim3(256), 0, st, p);
-    HIPCHK(h, hipGetLastError());
-    return AC_OK;
-}
-
-// a causal conv on a staged input: M outputs, output m reads staged rows [m*s, m*s + k) (no padding left)
-static int mstream_conv(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& xs, int k, int s, int M, Out out, int B, Act2* y,
-                        const Epi& epi = Epi{}) {
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(xs, s, s == 1 ? k : 2, PAD_ZERO, 0, 0, nullptr, 0, 0);
-    p.w = h->blob + g.w_off;
-    p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
-    p.y = out.raw;
-    p.y_elu = out.elu;
-    p.y_bs = (long long)M * g.N;
-    p.y_rs = g.N;
-    p.B = B;
-    p.M = M;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    p.scale = epi.scale;
-    p.res = epi.res;
-    p.res_bs = epi.res_bs;
-    p.res_rs = epi.res_rs;
-    const int rc = run_tap(h, st, p);
-    if (y) {
-        y->raw = Act{out.raw, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-        y->elu = Act{out.elu, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-    }
-    return rc;
+    return stream_stage(h, st, reinterpret_cast<float*>(state + Ls.conv[l]), reinterpret_cast<const int*>(state + Ls.fresh), Ls.conv_P[l], Ls.conv_C[l], l, x, B,
+                        staged, cap, replicate ? STAGE_REPLICATE : STAGE_ZERO, any_L);
 }
 
 struct MStreamScratch {   // transformer scratch (as mimi_path.hip's TfScratch)
     float *ln, *qkv, *att, *hid;
 };
-
-static Act staged_act(const float* p, int B, int rows, int C) { return Act{p, (long long)rows * C, C, rows, C}; }
 
 static void rope_inv(const ac_handle* h, float* inv) {   // mimi_finalize's inv_freq (the host override is gone after finalize)
     const ac_mimi_config& c = h->mcfg;
@@ -342,7 +280,7 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
                            Out{feats, nullptr}, B, nullptr)))
         return rc;
     ws.give(stg);
-    hipLaunchKernelGGL(mstream_advance_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
+    hipLaunchKernelGGL(mstream_advance_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
                        reinterpret_cast<int*>(state + Ls.fresh), B, T25);
     HIPCHK(h, hipGetLastError());
     return AC_OK;
@@ -423,7 +361,7 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
     ws.give(x);
     if ((rc = mstream_conv(h, st, m.dec_head, staged_act(stg, B, Ts + Ls.conv_P[l], Fh), c.last_kernel_size, 1, Ts, Out{sig, nullptr}, B, nullptr))) return rc;
     ws.give(stg);
-    hipLaunchKernelGGL(mstream_advance_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
+    hipLaunchKernelGGL(mstream_advance_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
                        reinterpret_cast<int*>(state + Ls.fresh), B, T25);
     HIPCHK(h, hipGetLastError());
     return AC_OK;
@@ -479,7 +417,7 @@ int ac_mimi_stream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int 
         return fail(h, AC_EINVAL, "ac_mimi_stream_reset: a masked reset needs a state this handle reset for B=%d before", B);
     char* s = static_cast<char*>(state_dev);
     MStreamHeader hd{MSTREAM_MAGIC, 1u, mstream_fingerprint(h->mcfg), B, 0};
-    hipLaunchKernelGGL(mstream_reset_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<MStreamHeader*>(s), hd,
+    hipLaunchKernelGGL(mstream_reset_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<MStreamHeader*>(s), hd,
                        reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh), reset_mask_dev, B);
     HIPCHK(h, hipGetLastError());
     h->mimi_streams[state_dev] = B;
@@ -538,7 +476,7 @@ int ac_mimi_stream_decode_reset(ac_handle* h, void* state_dev, size_t state_byte
         return fail(h, AC_EINVAL, "ac_mimi_stream_decode_reset: a masked reset needs a decode state this handle reset for B=%d before", B);
     char* s = static_cast<char*>(state_dev);
     MStreamHeader hd{MDSTREAM_MAGIC, 1u, mstream_fingerprint(h->mcfg), B, 0};
-    hipLaunchKernelGGL(mstream_reset_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<MStreamHeader*>(s), hd,
+    hipLaunchKernelGGL(mstream_reset_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<MStreamHeader*>(s), hd,
                        reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh), reset_mask_dev, B);
     HIPCHK(h, hipGetLastError());
     h->mimi_dstreams[state_dev] = B;

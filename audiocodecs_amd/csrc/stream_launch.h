@@ -1,0 +1,79 @@
+// Host side of stream_stage.h: the launch sequences the streaming paths share (mimi_stream.hip, encodec_stream.hip).
+#pragma once
+#include "core.h"
+#include "stream_stage.h"
+
+namespace acimpl {
+
+static unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 65536); }
+
+static Act staged_act(const float* p, int B, int rows, int C) { return Act{p, (long long)rows * C, C, rows, C}; }
+
+// [cache | x] -> staged (a fresh activation buffer of B * (P + L) * C floats); x's last P rows -> cache.  `cache` [B][P][C] and
+// `fresh` [B] live in the stream state; `mode` (STAGE_*) is a fresh stream's history.
+// (`any_L`: a chunk shorter than the history is staged in two launches -- stream_stage.h mstream_stage_ro_kernel)
+static int stream_stage(ac_handle* h, hipStream_t st, float* cache, const int* fresh, int P, int C, int l, const Act& x, int B, float* staged,
+                        size_t cap, int mode, bool any_L) {
+    MStreamStageParams p{};
+    p.P = P;
+    p.C = C;
+    if (x.C != p.C) return fail(h, AC_EINVAL, "stream stage %d: %d channels, cache holds %d", l, x.C, p.C);
+    if (x.L < p.P && !any_L) return fail(h, AC_EINVAL, "stream stage %d: %d rows per push, fewer than the %d history rows", l, x.L, p.P);
+    if ((size_t)B * (p.P + x.L) * p.C > cap) return fail(h, AC_ENOMEM, "stream stage %d exceeds its workspace buffer", l);
+    p.cache = cache;
+    p.x = x.p;
+    p.bs = x.bs;
+    p.ts = x.ts;
+    p.y = staged;
+    p.fresh = fresh;
+    p.B = B;
+    p.L = x.L;
+    p.replicate = mode;
+    const long long n = (long long)B * (p.P + x.L) * p.C;
+    if (x.L < p.P) {
+        {
+            ProfScope ps(h, st, "mstream_stage_ro_kernel", 0.0, 8.0 * n);
+            hipLaunchKernelGGL(mstream_stage_ro_kernel<>, dim3(grid_for(n)), dim3(256), 0, st, p);
+            HIPCHK(h, hipGetLastError());
+        }
+        const long long nc = (long long)B * p.P * p.C;
+        ProfScope ps(h, st, "mstream_cache_tail_kernel", 0.0, 8.0 * nc);
+        hipLaunchKernelGGL(mstream_cache_tail_kernel<>, dim3(grid_for(nc)), dim3(256), 0, st, p);
+        HIPCHK(h, hipGetLastError());
+        return AC_OK;
+    }
+    ProfScope ps(h, st, "mstream_stage_kernel", 0.0, 8.0 * n);
+    hipLaunchKernelGGL(mstream_stage_kernel<>, dim3(grid_for(n)), dim3(256), 0, st, p);
+    HIPCHK(h, hipGetLastError());
+    return AC_OK;
+}
+
+// a causal conv on a staged input: M outputs, output m reads staged rows [m*s, m*s + k) (no padding left)
+static int mstream_conv(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& xs, int k, int s, int M, Out out, int B, Act2* y,
+                        const Epi& epi = Epi{}) {
+    TapGemmParams p{};
+    p.nseg = 1;
+    p.seg[0] = make_seg(xs, s, s == 1 ? k : 2, PAD_ZERO, 0, 0, nullptr, 0, 0);
+    p.w = h->blob + g.w_off;
+    p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
+    p.y = out.raw;
+    p.y_elu = out.elu;
+    p.y_bs = (long long)M * g.N;
+    p.y_rs = g.N;
+    p.B = B;
+    p.M = M;
+    p.N = g.N;
+    p.Ktot = g.Ktot;
+    p.scale = epi.scale;
+    p.res = epi.res;
+    p.res_bs = epi.res_bs;
+    p.res_rs = epi.res_rs;
+    const int rc = run_tap(h, st, p);
+    if (y) {
+        y->raw = Act{out.raw, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
+        y->elu = Act{out.elu, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
+    }
+    return rc;
+}
+
+}  // namespace acimpl

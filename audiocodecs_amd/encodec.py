@@ -17,7 +17,7 @@ from . import _native, checkpoint
 from .codec import Codec
 from .config import ENCODEC_24KHZ, EncodecConfig
 
-__all__ = ["Encodec"]
+__all__ = ["Encodec", "EncodecEncodeStream", "EncodecDecodeStream"]
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -264,6 +264,34 @@ class Encodec(Codec):
             _native.check(nat.lib.ac_dequantize(nat.h, _ptr(toks), B, N, K, _ptr(out), _stream()), nat.h, "ac_dequantize")
         return out
 
+    # ---- streaming -------------------------------------------------------------------------------
+    def _stream_checks(self, what: str, batch_size, device) -> _Native:
+        need, lacks = ("encoder", "decode") if what == "encode_stream" else ("decoder", "encode")
+        if self.mode == lacks:
+            raise ValueError(f"{what} needs the {need}: this Encodec was built with mode=\"{lacks}\"")
+        if self.sample_rate != self.config.sampling_rate:
+            raise ValueError(
+                f"{what} runs at the codec's own rate ({self.config.sampling_rate} Hz) only: streaming resampling is not "
+                f"supported (sample_rate={self.sample_rate})"
+            )
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f"`batch_size` ({batch_size!r}) must be a positive int")
+        self._num_quantizers()
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return self._native_for(torch.empty(0, device=dev))
+
+    def encode_stream(self, batch_size: int, device=None) -> "EncodecEncodeStream":
+        """A stateful signal -> tokens encoder for `batch_size` independent streams on `device` (default: the current cuda
+        device).  Feed it with `push`; after the start-up hold of `WARMUP_FRAMES` frames every push returns the tokens of the
+        frames it completed (include/audiocodecs_amd.h ac_encodec_stream_*)."""
+        return EncodecEncodeStream(self, self._stream_checks("encode_stream", batch_size, device), batch_size)
+
+    def decode_stream(self, batch_size: int, device=None) -> "EncodecDecodeStream":
+        """A stateful tokens -> signal decoder for `batch_size` independent streams on `device` (default: the current cuda
+        device).  Feed it with `push`; after the start-up hold of `WARMUP_FRAMES` frames every push returns the samples of the
+        frames it was given (include/audiocodecs_amd.h ac_encodec_stream_decode*)."""
+        return EncodecDecodeStream(self, self._stream_checks("decode_stream", batch_size, device), batch_size)
+
     # ---- measurement hook used by bench.py ------------------------------------------------------
     def profile_kernels(self, fn):
         """Run fn() with per-kernel HIP-event timing armed; returns [(name, launches, ms, flops, bytes)]."""
@@ -276,3 +304,148 @@ class Encodec(Codec):
             n = nat.lib.ac_profile_end(nat.h, buf, 256)
         _native.check(n, nat.h, "ac_profile_end")
         return [(buf[i].name.decode(), buf[i].launches, buf[i].total_ms, buf[i].flops, buf[i].bytes) for i in range(n)]
+
+
+class _EncodecStream:
+    """What the two directions share: the device-side state block, the grow-only workspace and the warm-up rule.
+
+    EnCodec pads every causal conv by REFLECTION, so the first rows of a clip see a mirror image of the rows that follow them.  A
+    stream can reproduce that only once those rows are there: it holds back its first `WARMUP_FRAMES` = max(kernel_size,
+    last_kernel_size) frames (7 frames = 93 ms at 75 frames/s) and runs them as one push.  With fewer the reference itself switches
+    to its small-input padding rule and the one-shot result differs (tests/test_encodec_stream_oracle.py): the hold is the
+    reference's padding, not a choice of this library."""
+
+    def __init__(self, codec: Encodec, nat: _Native, batch_size: int, kind: str):
+        self.codec = codec
+        self._nat = nat
+        self.batch_size = batch_size
+        self.num_codebooks = codec._num_quantizers()
+        self.hop = codec.config.hop_length
+        self.WARMUP_FRAMES = max(codec.config.kernel_size, codec.config.last_kernel_size)
+        self.device = nat.device
+        L = nat.lib
+        self._fns = {
+            "encode": (L.ac_encodec_stream_state_bytes, L.ac_encodec_stream_reset, L.ac_encodec_stream_workspace_bytes, L.ac_encodec_stream_encode),
+            "decode": (L.ac_encodec_stream_decode_state_bytes, L.ac_encodec_stream_decode_reset, L.ac_encodec_stream_decode_workspace_bytes,
+                       L.ac_encodec_stream_decode),
+        }[kind]
+        self._kind = kind
+        nbytes = self._fns[0](nat.h, batch_size)
+        if nbytes == 0:
+            raise _native.NativeError(f"ac_encodec_stream_{'decode_' if kind == 'decode' else ''}state_bytes returned 0")
+        self._state_buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self._state_buf.data_ptr()) % 256
+        self._state = self._state_buf[off:off + nbytes]
+        self._ws = None
+        self.frames = 0          # frames run so far (the same for every slot)
+
+    def _reset_native(self, streams) -> None:
+        if streams is not None:
+            raise ValueError(
+                "EnCodec streams reset together: a slot restarted alone would sit in its warm-up hold while the others run "
+                "(`streams` must be None)"
+            )
+        nat = self._nat
+        with torch.cuda.device(self.device):
+            _native.check(self._fns[1](nat.h, _ptr(self._state), self._state.numel(), self.batch_size, None, _stream()), nat.h,
+                          f"ac_encodec_stream_{self._kind}_reset")
+        self.frames = 0
+
+    def _run(self, src: torch.Tensor, n: int, dst: torch.Tensor) -> None:
+        nat = self._nat
+        with torch.cuda.device(self.device):
+            need = self._fns[2](nat.h, self.batch_size, n)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            _native.check(self._fns[3](nat.h, _ptr(self._state), self._state.numel(), _ptr(src), self.batch_size, n, self.num_codebooks, _ptr(dst),
+                                       _ptr(self._ws), self._ws.numel(), _stream()), nat.h, f"ac_encodec_stream_{self._kind}")
+        self.frames += n
+
+
+class EncodecEncodeStream(_EncodecStream):
+    """Streaming EnCodec encode of `batch_size` streams (Encodec.encode_stream).  `push(sig)` takes [B, L] fp32 samples on the
+    codec's device, any L >= 0, and returns the int64 tokens [B, n, K] of the frames it releases (n may be 0).  Samples that do not
+    fill a frame wait here (`pending` samples).  A fresh stream releases nothing until `WARMUP_FRAMES` whole frames are in (the
+    reference's reflect padding: 93 ms); the push that crosses that mark returns all frames completed so far, and from then on every
+    frame comes out in the push that completes it.  The tokens of a stream are those `sig_to_toks` gives on its whole signal (up to
+    near-ties: scales are taken per push), however it was split into pushes and whatever the other streams carry.  The stream state
+    and the workspace are device tensors owned by this object."""
+
+    def __init__(self, codec: Encodec, nat: _Native, batch_size: int):
+        super().__init__(codec, nat, batch_size, "encode")
+        self._pending = torch.empty(batch_size, 0, dtype=torch.float32, device=self.device)
+        self.reset()
+
+    @property
+    def pending(self) -> int:
+        return int(self._pending.shape[1])
+
+    @torch.no_grad()
+    def reset(self, streams=None) -> None:
+        """Start all streams afresh, dropping what is pending (held warm-up frames included).  `streams` must be None."""
+        self._reset_native(streams)
+        self._pending = self._pending[:, :0]
+
+    @torch.no_grad()
+    def push(self, sig: torch.Tensor) -> torch.Tensor:
+        B, hop, K = self.batch_size, self.hop, self.num_codebooks
+        if not isinstance(sig, torch.Tensor) or sig.dim() != 2 or sig.shape[0] != B:
+            raise ValueError(f"push expects a [{B}, L] tensor, got {tuple(sig.shape) if isinstance(sig, torch.Tensor) else type(sig)}")
+        if sig.dtype != torch.float32:
+            raise ValueError(f"push expects float32 samples, got {sig.dtype}")
+        if sig.device != self.device:
+            raise ValueError(f"push expects samples on {self.device}, got {sig.device}")
+        n = (self.pending + sig.shape[1]) // hop
+        if n == 0 or (self.frames == 0 and n < self.WARMUP_FRAMES):
+            self._pending = torch.cat([self._pending, sig], 1) if sig.shape[1] else self._pending
+            return torch.empty(B, 0, K, dtype=torch.int64, device=self.device)
+        whole = torch.cat([self._pending, sig], 1) if self.pending else sig
+        chunk = whole[:, : n * hop].contiguous()
+        toks = torch.empty(B, n, K, dtype=torch.int64, device=self.device)
+        self._run(chunk, n, toks)
+        self._pending = whole[:, n * hop:].clone()
+        return toks
+
+
+class EncodecDecodeStream(_EncodecStream):
+    """Streaming EnCodec decode of `batch_size` streams (Encodec.decode_stream).  `push(toks)` takes [B, F, K] int64 tokens on the
+    codec's device, K = the codec's stage count, any F >= 0, and returns [B, n * hop] fp32 samples.  A fresh stream holds its first
+    tokens back (`pending_frames`) until `WARMUP_FRAMES` frames are in (the reference's reflect padding), returns the samples of all
+    of them with the push that crosses that mark, and F * hop samples per push from then on.  The samples of a stream are those
+    `toks_to_sig` gives on its whole token sequence (up to rounding), whatever the other streams carry.  The stream state and the
+    workspace are device tensors owned by this object."""
+
+    def __init__(self, codec: Encodec, nat: _Native, batch_size: int):
+        super().__init__(codec, nat, batch_size, "decode")
+        self._held = torch.empty(batch_size, 0, self.num_codebooks, dtype=torch.int64, device=self.device)
+        self.reset()
+
+    @property
+    def pending_frames(self) -> int:
+        return int(self._held.shape[1])
+
+    @torch.no_grad()
+    def reset(self, streams=None) -> None:
+        """Start all streams afresh, dropping the held warm-up frames.  `streams` must be None."""
+        self._reset_native(streams)
+        self._held = self._held[:, :0]
+
+    @torch.no_grad()
+    def push(self, toks: torch.Tensor) -> torch.Tensor:
+        B, hop, K = self.batch_size, self.hop, self.num_codebooks
+        if not isinstance(toks, torch.Tensor) or toks.dim() != 3 or toks.shape[0] != B or toks.shape[2] != K:
+            raise ValueError(f"push expects a [{B}, F, {K}] tensor, got {tuple(toks.shape) if isinstance(toks, torch.Tensor) else type(toks)}")
+        if toks.dtype != torch.int64:
+            raise ValueError(f"push expects int64 tokens, got {toks.dtype}")
+        if toks.device != self.device:
+            raise ValueError(f"push expects tokens on {self.device}, got {toks.device}")
+        n = self.pending_frames + toks.shape[1]
+        if n == 0 or (self.frames == 0 and n < self.WARMUP_FRAMES):
+            self._held = torch.cat([self._held, toks], 1) if toks.shape[1] else self._held
+            return torch.empty(B, 0, dtype=torch.float32, device=self.device)
+        chunk = (torch.cat([self._held, toks], 1) if self.pending_frames else toks).contiguous()
+        sig = torch.empty(B, n * hop, dtype=torch.float32, device=self.device)
+        self._run(chunk, n, sig)
+        self._held = self._held[:, :0]
+        return sig

@@ -325,6 +325,32 @@ size_t ac_mimi_stream_decode_workspace_bytes(const ac_handle* h, int B, int F);
 int ac_mimi_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K,
                           float* sig_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Streaming EnCodec encode and decode: the same contract as the Mimi calls above on an EnCodec handle -- B streams, F whole frames per
+ * stream and push, tokens [B,F,K] and samples [B, F * hop] in ac_encode's / ac_decode's layouts; the caller owns the state
+ * (ac_encodec_stream_state_bytes / _decode_state_bytes(h, B) bytes, 256-byte aligned) and the workspace (_workspace_bytes(h, B, F));
+ * nothing allocates or synchronises.  Per stream the state holds the last k - stride input rows of every causal conv, the previous
+ * input row of every transposed conv, h and c of both LSTM layers (zero after a reset), the frame count and a "fresh" flag
+ * (DESIGN.md "Streaming EnCodec").  An encode state and a decode state have their own magic and layout and are registered separately.
+ * EnCodec pads by reflection, so a fresh stream's conv history is the mirror image of its own first rows, and the FIRST push after a
+ * reset must bring F >= max(kernel_size, last_kernel_size) frames (7: 93 ms; AC_EINVAL otherwise -- with fewer the reference itself
+ * switches to its small-input padding rule and no stream could reproduce the one-shot result).  From then on any F >= 1; the tokens /
+ * samples of a stream are those ac_encode / ac_decode give on its whole signal / token sequence (up to rounding: split16 scales are
+ * taken per stream and push) and do not depend on the other streams.  The streams of a state reset together: reset_mask_dev must be
+ * NULL (AC_EINVAL).  AC_EINVAL for a non-EnCodec handle (*_state_bytes and *_workspace_bytes return 0), a state this handle never
+ * reset, reset for another B or reset as the other kind; AC_ENOMEM for a state or workspace that is too small; AC_ESTATE for a handle
+ * loaded without the half it needs.  These are decided on the host before anything is launched: the handle and the state stay as
+ * they were. */
+size_t ac_encodec_stream_state_bytes(const ac_handle* h, int B);
+int ac_encodec_stream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, const uint8_t* reset_mask_dev, void* stream);
+size_t ac_encodec_stream_workspace_bytes(const ac_handle* h, int B, int F);
+int ac_encodec_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, const float* sig_dev, int B, int F, int K,
+                             int64_t* toks_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t ac_encodec_stream_decode_state_bytes(const ac_handle* h, int B);
+int ac_encodec_stream_decode_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, const uint8_t* reset_mask_dev, void* stream);
+size_t ac_encodec_stream_decode_workspace_bytes(const ac_handle* h, int B, int F);
+int ac_encodec_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K,
+                             float* sig_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Copy the first K codebooks to embs_dev [K, codebook_size, ac_codebook_dim] fp32 (encodec.py:74-79;
  * mimi.py:52-62 `latent=True`). */
 int ac_embs(ac_handle* h, int K, float* embs_dev, void* stream);
