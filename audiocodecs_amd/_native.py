@@ -126,7 +126,7 @@ class AcKernelStat(C.Structure):
     ]
 
 
-_vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
+_vp, _i, _sz, _ll = C.c_void_p, C.c_int, C.c_size_t, C.c_longlong
 # name -> (restype, argtypes): every symbol include/audiocodecs_amd.h declares
 EXPORTS = {
     "ac_version": (_i, []),
@@ -174,6 +174,10 @@ EXPORTS = {
     "ac_embs": (_i, [_vp, _i, _vp, _vp]),
     "ac_embs_projected": (_i, [_vp, _i, _vp, _vp]),
     "ac_resample": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "ac_resample_stream_out_len": (_ll, [_ll, _i, _i, _i, _i, _i]),
+    "ac_resample_stream_state_bytes": (_sz, [_i, _i]),
+    "ac_resample_stream_reset": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "ac_resample_stream_push": (_i, [_vp, _sz, _vp, _ll, _i, _i, _ll, _vp, _i, _i, _i, _i, _vp, _ll, _ll, _i, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

@@ -684,6 +684,43 @@ int ac_resample(const float* x, int B, int L, const float* kern, int n, int o, i
     return resample_launch(x, B, L, kern, n, o, taps, width, y, L_out, (hipStream_t)stream);
 }
 
+// ---- the stateful resampler: handle-free like ac_resample; every refusal is decided here, before anything is launched
+static bool rstream_geometry_ok(int B, int n, int o, int taps, int width) {
+    return B >= 1 && n >= 1 && o >= 1 && width >= 0 && taps == 2 * (long long)width + o && taps <= RSTREAM_MAX_TAPS;
+}
+
+long long ac_resample_stream_out_len(long long consumed, int L, int n, int o, int width, int finish) {
+    if (consumed < 0 || L < 0 || n < 1 || o < 1 || width < 0) return AC_EINVAL;
+    if (consumed > (1ll << 62) / n - L) return AC_EINVAL;
+    return resample_stream_out_len(consumed, L, n, o, width, finish);
+}
+
+size_t ac_resample_stream_state_bytes(int B, int taps) {
+    if (B < 1 || taps < 1 || taps > RSTREAM_MAX_TAPS) return 0;
+    return resample_stream_state_bytes(B, taps);
+}
+
+int ac_resample_stream_reset(void* state_dev, size_t state_bytes, int B, int n, int o, int taps, int width, void* stream) {
+    if (!state_dev || (reinterpret_cast<uintptr_t>(state_dev) & 255) != 0 || !rstream_geometry_ok(B, n, o, taps, width)) return AC_EINVAL;
+    if (state_bytes < resample_stream_state_bytes(B, taps)) return AC_ENOMEM;
+    return resample_stream_reset_launch(state_dev, B, n, o, taps, width, (hipStream_t)stream);
+}
+
+int ac_resample_stream_push(void* state_dev, size_t state_bytes, const float* x_dev, long long x_pitch, int B, int L, long long consumed,
+                            const float* kern_dev, int n, int o, int taps, int width, float* y_dev, long long y_pitch, long long y_capacity,
+                            int finish, void* stream) {
+    if (!state_dev || (reinterpret_cast<uintptr_t>(state_dev) & 255) != 0 || !kern_dev || !rstream_geometry_ok(B, n, o, taps, width)) return AC_EINVAL;
+    if (L < 0 || consumed < 0 || (L > 0 && (!x_dev || x_pitch < L))) return AC_EINVAL;
+    if (state_bytes < resample_stream_state_bytes(B, taps)) return AC_ENOMEM;
+    const long long m = ac_resample_stream_out_len(consumed, L, n, o, width, finish);
+    if (m < 0 || m > 0x7fffffffll - 256) return AC_EINVAL;
+    if (m > 0 && (!y_dev || y_pitch < m)) return AC_EINVAL;
+    if (y_capacity < m) return AC_ENOMEM;
+    if (L == 0 && !finish) return AC_OK;          // nothing to take in, nothing complete: the state stays as it is
+    return resample_stream_push_launch(state_dev, x_dev, x_pitch, B, L, consumed, kern_dev, n, o, taps, width, y_dev, y_pitch, (int)m, finish ? 1 : 0,
+                                       (hipStream_t)stream);
+}
+
 const char* ac_last_error(const ac_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
 void ac_destroy(ac_handle* h) {

@@ -997,6 +997,14 @@ int rvq_encode_cdist_launch(ac_handle* h, hipStream_t st, const RvqEncParams& p,
 void rvq_decode_launch(hipStream_t st, const RvqDecParams& p, unsigned blocks);
 void amax_fill_launch(hipStream_t st, unsigned* slot, unsigned bits, int B);
 int resample_launch(const float* x, int B, int L, const float* kern, int n, int o, int taps, int width, float* y, int L_out, hipStream_t st);
+// the stateful form (thin.h): pure host arithmetic of a push, the state's size, and the launches (nothing is checked there: ac_api.hip does)
+constexpr int RSTREAM_MAX_TAPS = 8192;   // a history row goes through LDS when a push moves it on: 32 KiB
+long long resample_stream_groups(long long total, int o, int width);
+long long resample_stream_out_len(long long consumed, int L, int n, int o, int width, int finish);
+size_t resample_stream_state_bytes(int B, int taps);
+int resample_stream_reset_launch(void* state, int B, int n, int o, int taps, int width, hipStream_t st);
+int resample_stream_push_launch(void* state, const float* x, long long x_pitch, int B, int L, long long consumed, const float* kern, int n, int o, int taps,
+                                int width, float* y, long long y_pitch, int m, int finish, hipStream_t st);
 
 // ---- per-codec paths (mimi_path.hip, dac_path.hip, wavtok_path.hip)
 // optional epilogue terms of a tap-GEMM launch (Mimi's transformers, WavTokenizer's backbone, DAC's residual units)

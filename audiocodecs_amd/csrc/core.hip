@@ -1512,6 +1512,36 @@ int resample_launch(const float* x, int B, int L, const float* kern, int n, int 
     hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((L_out + 255) / 256), B), dim3(256), 0, st, p);
     return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
 }
+long long resample_stream_groups(long long total, int o, int width) {
+    return total < (long long)width + o ? 0 : (total - width - o) / o + 1;
+}
+long long resample_stream_out_len(long long consumed, int L, int n, int o, int width, int finish) {
+    const long long total = consumed + L, out0 = n * resample_stream_groups(consumed, o, width);
+    const long long out1 = finish ? (n * total + o - 1) / o : n * resample_stream_groups(total, o, width);
+    return out1 - out0;
+}
+static size_t rstream_align(size_t v) { return (v + 255) & ~(size_t)255; }
+size_t resample_stream_state_bytes(int B, int taps) {
+    return 256 + rstream_align(sizeof(long long) * (size_t)B) + rstream_align(sizeof(float) * (size_t)B * (size_t)(taps - 1));
+}
+int resample_stream_reset_launch(void* state, int B, int n, int o, int taps, int width, hipStream_t st) {
+    char* s = static_cast<char*>(state);
+    static_assert(sizeof(RStreamHeader) <= 256, "the header has 256 bytes");
+    const RStreamHeader hd{RSTREAM_MAGIC, B, n, o, taps, width};
+    hipLaunchKernelGGL(resample_stream_reset_kernel, dim3(B), dim3(256), 0, st, reinterpret_cast<RStreamHeader*>(s), hd,
+                       reinterpret_cast<long long*>(s + 256), reinterpret_cast<float*>(s + 256 + rstream_align(sizeof(long long) * (size_t)B)));
+    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+}
+int resample_stream_push_launch(void* state, const float* x, long long x_pitch, int B, int L, long long consumed, const float* kern, int n, int o, int taps,
+                                int width, float* y, long long y_pitch, int m, int finish, hipStream_t st) {
+    char* s = static_cast<char*>(state);
+    ResampleStreamParams p{x, kern, y, reinterpret_cast<const RStreamHeader*>(s), reinterpret_cast<long long*>(s + 256),
+                           reinterpret_cast<float*>(s + 256 + rstream_align(sizeof(long long) * (size_t)B)), consumed,
+                           n * resample_stream_groups(consumed, o, width), x_pitch, y_pitch, B, L, m, n, o, taps, width, finish};
+    if (m > 0) hipLaunchKernelGGL(resample_stream_kernel, dim3((unsigned)((m + 255) / 256), B), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(resample_stream_hist_kernel, dim3(B), dim3(256), sizeof(float) * (size_t)(taps - 1), st, p);
+    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+}
 void amax_fill_launch(hipStream_t st, unsigned* slot, unsigned bits, int B) {
     hipLaunchKernelGGL(amax_fill_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, slot, bits, B);
 }

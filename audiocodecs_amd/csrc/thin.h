@@ -203,4 +203,99 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleParams p) {
     p.y[(long long)b * p.L_out + gid] = acc;
 }
 
+// The same conversion, push by push (ac_resample_stream_*).  Output group i (the n outputs i*n .. i*n + n - 1)
+// reads the inputs i*o - width .. i*o - width + taps - 1; it is complete once width + o + i*o samples are in, so after `total` samples
+// G(total) = total < width + o ? 0 : (total - width - o) / o + 1 groups are, and a push emits the groups G(before) .. G(after) - 1.
+// The oldest input a later group still needs lies fewer than taps samples back: the state keeps the last taps - 1 samples per stream
+// (zeros before the stream's start).  A closing push takes all later input as zero and emits up to ceil(n * total / o) outputs.
+//
+// State (device memory of the caller, 256-byte aligned):
+//   [0, 256)                        RStreamHeader: written by a reset, read-only afterwards
+//   [256, 256 + align256(8 B))      consumed[B]: input samples taken so far per stream, RSTREAM_FINISHED after the closing push
+//   [.., + align256(4 B (taps-1)))  hist[B][taps - 1]: the last taps - 1 input samples, oldest first
+// A push is two launches: resample_stream_kernel reads hist and the chunk and writes the outputs; resample_stream_hist_kernel, one
+// workgroup per stream, then moves hist on (through LDS: a chunk shorter than the history shifts it in place) and advances consumed[b].
+// Both check the header and their stream's count against the call's arguments (the only writer of consumed[b] is workgroup b of the
+// second launch, so no workgroup reads a word another one writes in the same launch); on a mismatch the first writes NaN to its outputs
+// and the second leaves the state as it is.
+constexpr unsigned RSTREAM_MAGIC = 0x54535352u;    // "RSST"
+constexpr long long RSTREAM_FINISHED = -1;
+
+struct RStreamHeader {
+    unsigned magic;
+    int B, n, o, taps, width;
+};
+
+struct ResampleStreamParams {
+    const float* x;          // [B][x_pitch]: L new samples per stream
+    const float* kern;       // [n][taps]
+    float* y;                // [B][y_pitch]: this push's m outputs per stream
+    const RStreamHeader* hdr;
+    long long* consumed;     // [B]
+    float* hist;             // [B][taps - 1]
+    long long before;        // samples consumed before this push (the caller's count)
+    long long out0;          // absolute index of this push's first output: n * G(before)
+    long long x_pitch, y_pitch;
+    int B, L, m, n, o, taps, width, finish;
+};
+
+__device__ __forceinline__ bool rstream_state_ok(const ResampleStreamParams& p, int b) {
+    const RStreamHeader h = *p.hdr;
+    return h.magic == RSTREAM_MAGIC && h.B == p.B && h.n == p.n && h.o == p.o && h.taps == p.taps && h.width == p.width &&
+           p.consumed[b] == p.before;
+}
+
+__global__ __launch_bounds__(256) void resample_stream_kernel(const ResampleStreamParams p) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (j >= p.m) return;
+    float* yb = p.y + (long long)b * p.y_pitch;
+    if (!rstream_state_ok(p, b)) {
+        yb[j] = __builtin_nanf("");
+        return;
+    }
+    const long long gid = p.out0 + j;
+    const long long i = gid / p.n;
+    const int ph = (int)(gid % p.n);
+    const int H = p.taps - 1;
+    const float* xb = p.x + (long long)b * p.x_pitch;
+    const float* hb = p.hist + (long long)b * H;
+    const float* kr = p.kern + (long long)ph * p.taps;
+    // position of tap 0 relative to the chunk's first sample; >= -H because group i was not complete before this push
+    const int base = (int)(i * p.o - p.width - p.before);
+    float acc = 0.f;
+    for (int k = 0; k < p.taps; ++k) {     // ascending k, one fmaf per tap: resample_kernel's chain (a stored zero where it skips)
+        const int m = base + k;
+        if (m < 0) acc = fmaf(kr[k], hb[H + m], acc);
+        else if (m < p.L) acc = fmaf(kr[k], xb[m], acc);
+    }
+    yb[j] = acc;
+}
+
+__global__ __launch_bounds__(256) void resample_stream_hist_kernel(const ResampleStreamParams p) {
+    extern __shared__ __align__(16) float rs_row[];      // [taps - 1]
+    const int b = blockIdx.x;
+    if (!rstream_state_ok(p, b)) return;                 // (uniform over the workgroup)
+    const int H = p.taps - 1;
+    const float* xb = p.x + (long long)b * p.x_pitch;
+    float* hb = p.hist + (long long)b * H;
+    for (int j = threadIdx.x; j < H; j += 256) {         // new hist[j] = (old hist ++ chunk)[j + L]
+        const long long s = (long long)j + p.L;
+        rs_row[j] = s < H ? hb[s] : xb[s - H];
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < H; j += 256) hb[j] = rs_row[j];
+    if (threadIdx.x == 0) p.consumed[b] = p.finish ? RSTREAM_FINISHED : p.before + p.L;
+}
+
+__global__ __launch_bounds__(256) void resample_stream_reset_kernel(RStreamHeader* hdr, const RStreamHeader hd, long long* consumed, float* hist) {
+    const int b = blockIdx.x;
+    float* hb = hist + (long long)b * (hd.taps - 1);
+    for (int j = threadIdx.x; j < hd.taps - 1; j += 256) hb[j] = 0.f;
+    if (threadIdx.x == 0) {
+        consumed[b] = 0;
+        if (b == 0) *hdr = hd;
+    }
+}
+
 }  // namespace ac

@@ -16,6 +16,7 @@ import torch
 from . import _native, checkpoint
 from .codec import Codec
 from .config import ENCODEC_24KHZ, EncodecConfig
+from .resample import ResampleStream
 
 __all__ = ["Encodec", "EncodecEncodeStream", "EncodecDecodeStream"]
 
@@ -265,14 +266,14 @@ class Encodec(Codec):
         return out
 
     # ---- streaming -------------------------------------------------------------------------------
-    def _stream_checks(self, what: str, batch_size, device) -> _Native:
+    def _stream_checks(self, what: str, batch_size, device, resample=False) -> _Native:
         need, lacks = ("encoder", "decode") if what == "encode_stream" else ("decoder", "encode")
         if self.mode == lacks:
             raise ValueError(f"{what} needs the {need}: this Encodec was built with mode=\"{lacks}\"")
-        if self.sample_rate != self.config.sampling_rate:
+        if self.sample_rate != self.config.sampling_rate and not resample:
             raise ValueError(
-                f"{what} runs at the codec's own rate ({self.config.sampling_rate} Hz) only: streaming resampling is not "
-                f"supported (sample_rate={self.sample_rate})"
+                f"{what} runs at the codec's own rate ({self.config.sampling_rate} Hz): streaming resampling from or to "
+                f"sample_rate={self.sample_rate} is opt-in, pass resample=True"
             )
         if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
             raise ValueError(f"`batch_size` ({batch_size!r}) must be a positive int")
@@ -280,17 +281,19 @@ class Encodec(Codec):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         return self._native_for(torch.empty(0, device=dev))
 
-    def encode_stream(self, batch_size: int, device=None) -> "EncodecEncodeStream":
+    def encode_stream(self, batch_size: int, device=None, *, resample: bool = False) -> "EncodecEncodeStream":
         """A stateful signal -> tokens encoder for `batch_size` independent streams on `device` (default: the current cuda
         device).  Feed it with `push`; after the start-up hold of `WARMUP_FRAMES` frames every push returns the tokens of the
-        frames it completed (include/audiocodecs_amd.h ac_encodec_stream_*)."""
-        return EncodecEncodeStream(self, self._stream_checks("encode_stream", batch_size, device), batch_size)
+        frames it completed (include/audiocodecs_amd.h ac_encodec_stream_*).  `resample=True`: the
+        pushes are at `sample_rate` and go through a `ResampleStream` to the codec's rate first (close the stream with `finish`)."""
+        return EncodecEncodeStream(self, self._stream_checks("encode_stream", batch_size, device, resample), batch_size, bool(resample))
 
-    def decode_stream(self, batch_size: int, device=None) -> "EncodecDecodeStream":
+    def decode_stream(self, batch_size: int, device=None, *, resample: bool = False) -> "EncodecDecodeStream":
         """A stateful tokens -> signal decoder for `batch_size` independent streams on `device` (default: the current cuda
         device).  Feed it with `push`; after the start-up hold of `WARMUP_FRAMES` frames every push returns the samples of the
-        frames it was given (include/audiocodecs_amd.h ac_encodec_stream_decode*)."""
-        return EncodecDecodeStream(self, self._stream_checks("decode_stream", batch_size, device), batch_size)
+        frames it was given (include/audiocodecs_amd.h ac_encodec_stream_decode*).  `resample=True`:
+        the samples come out at `sample_rate`, through a `ResampleStream` behind the decoder (`finish` returns its tail)."""
+        return EncodecDecodeStream(self, self._stream_checks("decode_stream", batch_size, device, resample), batch_size, bool(resample))
 
     # ---- measurement hook used by bench.py ------------------------------------------------------
     def profile_kernels(self, fn):
@@ -315,7 +318,7 @@ class _EncodecStream:
     to its small-input padding rule and the one-shot result differs (tests/test_encodec_stream_oracle.py): the hold is the
     reference's padding, not a choice of this library."""
 
-    def __init__(self, codec: Encodec, nat: _Native, batch_size: int, kind: str):
+    def __init__(self, codec: Encodec, nat: _Native, batch_size: int, kind: str, resample: bool = False):
         self.codec = codec
         self._nat = nat
         self.batch_size = batch_size
@@ -338,6 +341,16 @@ class _EncodecStream:
         self._state = self._state_buf[off:off + nbytes]
         self._ws = None
         self.frames = 0          # frames run so far (the same for every slot)
+        # resample=True at another rate than the codec's: the boundary's resampler, in front of the encoder or behind the decoder
+        self._rs = None
+        self._finished = False
+        rate, own = int(codec.sample_rate), int(codec.config.sampling_rate)
+        if resample and rate != own:
+            self._rs = ResampleStream(rate, own, batch_size, self.device) if kind == "encode" else ResampleStream(own, rate, batch_size, self.device)
+
+    def _open(self, what: str) -> None:
+        if self._finished:
+            raise ValueError(f"{what} after finish: the stream is closed (call reset() first)")
 
     def _reset_native(self, streams) -> None:
         if streams is not None:
@@ -350,6 +363,9 @@ class _EncodecStream:
             _native.check(self._fns[1](nat.h, _ptr(self._state), self._state.numel(), self.batch_size, None, _stream()), nat.h,
                           f"ac_encodec_stream_{self._kind}_reset")
         self.frames = 0
+        self._finished = False
+        if self._rs is not None:
+            self._rs.reset()
 
     def _run(self, src: torch.Tensor, n: int, dst: torch.Tensor) -> None:
         nat = self._nat
@@ -370,10 +386,15 @@ class EncodecEncodeStream(_EncodecStream):
     reference's reflect padding: 93 ms); the push that crosses that mark returns all frames completed so far, and from then on every
     frame comes out in the push that completes it.  The tokens of a stream are those `sig_to_toks` gives on its whole signal (up to
     near-ties: scales are taken per push), however it was split into pushes and whatever the other streams carry.  The stream state
-    and the workspace are device tensors owned by this object."""
+    and the workspace are device tensors owned by this object.
 
-    def __init__(self, codec: Encodec, nat: _Native, batch_size: int):
-        super().__init__(codec, nat, batch_size, "encode")
+    With `resample=True` on a codec whose `sample_rate` is not the model's, `push` takes samples at `sample_rate`; they pass a
+    `ResampleStream` (0.5 ms of added latency for 16 -> 24 kHz) and the frame and warm-up rules above then count resampled samples.
+    `finish()` flushes the resampler's tail into the encoder and returns the tokens of any frame that completes; a trailing partial
+    frame stays `pending`.  After `finish` only `reset` is accepted."""
+
+    def __init__(self, codec: Encodec, nat: _Native, batch_size: int, resample: bool = False):
+        super().__init__(codec, nat, batch_size, "encode", resample)
         self._pending = torch.empty(batch_size, 0, dtype=torch.float32, device=self.device)
         self.reset()
 
@@ -389,13 +410,42 @@ class EncodecEncodeStream(_EncodecStream):
 
     @torch.no_grad()
     def push(self, sig: torch.Tensor) -> torch.Tensor:
-        B, hop, K = self.batch_size, self.hop, self.num_codebooks
+        B = self.batch_size
         if not isinstance(sig, torch.Tensor) or sig.dim() != 2 or sig.shape[0] != B:
             raise ValueError(f"push expects a [{B}, L] tensor, got {tuple(sig.shape) if isinstance(sig, torch.Tensor) else type(sig)}")
         if sig.dtype != torch.float32:
             raise ValueError(f"push expects float32 samples, got {sig.dtype}")
         if sig.device != self.device:
             raise ValueError(f"push expects samples on {self.device}, got {sig.device}")
+        self._open("push")
+        return self._take(self._resampled(sig, False) if self._rs is not None else sig)
+
+    @torch.no_grad()
+    def finish(self) -> torch.Tensor:
+        """Close the streams: the resampler's tail goes through the encoder; returns the tokens [B, n, K] of the frames it completes."""
+        self._open("finish")
+        toks = self._take(self._resampled(None, True) if self._rs is not None
+                          else torch.empty(self.batch_size, 0, dtype=torch.float32, device=self.device))
+        self._finished = True
+        return toks
+
+    def _resampled(self, sig, finish: bool) -> torch.Tensor:
+        """The pending samples with the resampler's output for this push written straight behind them (one buffer, no second copy)."""
+        rs, pend = self._rs, self.pending
+        m = rs.out_len(0 if finish else sig.shape[1], finish)
+        whole = torch.empty(self.batch_size, pend + m, dtype=torch.float32, device=self.device)
+        if pend:
+            whole[:, :pend].copy_(self._pending)
+        if finish:
+            rs.finish(out=whole[:, pend:])
+        else:
+            rs.push(sig, out=whole[:, pend:])
+        self._pending = self._pending[:, :0]
+        return whole
+
+    def _take(self, sig: torch.Tensor) -> torch.Tensor:
+        """Samples at the codec's rate: run the frames they complete, keep the rest pending."""
+        B, hop, K = self.batch_size, self.hop, self.num_codebooks
         n = (self.pending + sig.shape[1]) // hop
         if n == 0 or (self.frames == 0 and n < self.WARMUP_FRAMES):
             self._pending = torch.cat([self._pending, sig], 1) if sig.shape[1] else self._pending
@@ -414,10 +464,14 @@ class EncodecDecodeStream(_EncodecStream):
     tokens back (`pending_frames`) until `WARMUP_FRAMES` frames are in (the reference's reflect padding), returns the samples of all
     of them with the push that crosses that mark, and F * hop samples per push from then on.  The samples of a stream are those
     `toks_to_sig` gives on its whole token sequence (up to rounding), whatever the other streams carry.  The stream state and the
-    workspace are device tensors owned by this object."""
+    workspace are device tensors owned by this object.
 
-    def __init__(self, codec: Encodec, nat: _Native, batch_size: int):
-        super().__init__(codec, nat, batch_size, "decode")
+    With `resample=True` on a codec whose `sample_rate` is not the model's, the samples pass a `ResampleStream` to `sample_rate` on
+    their way out: a push returns what the resampler has completed (the count varies), `finish()` its tail, and everything together
+    has the length `toks_to_sig` returns.  After `finish` only `reset` is accepted."""
+
+    def __init__(self, codec: Encodec, nat: _Native, batch_size: int, resample: bool = False):
+        super().__init__(codec, nat, batch_size, "decode", resample)
         self._held = torch.empty(batch_size, 0, self.num_codebooks, dtype=torch.int64, device=self.device)
         self.reset()
 
@@ -433,13 +487,28 @@ class EncodecDecodeStream(_EncodecStream):
 
     @torch.no_grad()
     def push(self, toks: torch.Tensor) -> torch.Tensor:
-        B, hop, K = self.batch_size, self.hop, self.num_codebooks
+        B, K = self.batch_size, self.num_codebooks
         if not isinstance(toks, torch.Tensor) or toks.dim() != 3 or toks.shape[0] != B or toks.shape[2] != K:
             raise ValueError(f"push expects a [{B}, F, {K}] tensor, got {tuple(toks.shape) if isinstance(toks, torch.Tensor) else type(toks)}")
         if toks.dtype != torch.int64:
             raise ValueError(f"push expects int64 tokens, got {toks.dtype}")
         if toks.device != self.device:
             raise ValueError(f"push expects tokens on {self.device}, got {toks.device}")
+        self._open("push")
+        sig = self._decode(toks)
+        return self._rs.push(sig) if self._rs is not None else sig
+
+    @torch.no_grad()
+    def finish(self) -> torch.Tensor:
+        """Close the streams: the resampler's tail [B, m] (nothing without one).  Held warm-up frames are not decoded."""
+        self._open("finish")
+        self._finished = True
+        if self._rs is not None:
+            return self._rs.finish()
+        return torch.empty(self.batch_size, 0, dtype=torch.float32, device=self.device)
+
+    def _decode(self, toks: torch.Tensor) -> torch.Tensor:
+        B, hop, K = self.batch_size, self.hop, self.num_codebooks
         n = self.pending_frames + toks.shape[1]
         if n == 0 or (self.frames == 0 and n < self.WARMUP_FRAMES):
             self._held = torch.cat([self._held, toks], 1) if toks.shape[1] else self._held

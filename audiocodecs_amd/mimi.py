@@ -17,6 +17,7 @@ from . import _native
 from .codec import Codec
 from .config import MIMI_24KHZ, MimiConfig
 from .encodec import _ptr, _stream
+from .resample import ResampleStream
 
 __all__ = ["Mimi", "MimiEncodeStream", "MimiDecodeStream"]
 
@@ -235,40 +236,42 @@ class Mimi(Codec):
         return out
 
     # ---- streaming encode ------------------------------------------------------------------------
-    def encode_stream(self, batch_size: int, device=None) -> "MimiEncodeStream":
+    def encode_stream(self, batch_size: int, device=None, *, resample: bool = False) -> "MimiEncodeStream":
         """A stateful signal -> tokens encoder for `batch_size` independent streams on `device` (default: the current cuda
         device).  Feed it with `push`; every push returns the tokens of the frames it completed (include/audiocodecs_amd.h
-        ac_mimi_stream_*)."""
+        ac_mimi_stream_*).  `resample=True`: the pushes are at `sample_rate` and go through a
+        `ResampleStream` to the codec's rate first (close the stream with `finish`)."""
         if self.mode == "decode":
             raise ValueError("encode_stream needs the encoder: this Mimi was built with mode=\"decode\"")
-        if self.sample_rate != self.config.sampling_rate:
+        if self.sample_rate != self.config.sampling_rate and not resample:
             raise ValueError(
-                f"encode_stream runs at the codec's own rate ({self.config.sampling_rate} Hz) only: streaming resampling is not "
-                f"supported (sample_rate={self.sample_rate})"
+                f"encode_stream runs at the codec's own rate ({self.config.sampling_rate} Hz): streaming resampling from or to "
+                f"sample_rate={self.sample_rate} is opt-in, pass resample=True"
             )
         if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
             raise ValueError(f"`batch_size` ({batch_size!r}) must be a positive int")
         self._check_num_codebooks()
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return MimiEncodeStream(self, self._native_for(torch.empty(0, device=dev)), batch_size)
+        return MimiEncodeStream(self, self._native_for(torch.empty(0, device=dev)), batch_size, bool(resample))
 
     # ---- streaming decode ------------------------------------------------------------------------
-    def decode_stream(self, batch_size: int, device=None) -> "MimiDecodeStream":
+    def decode_stream(self, batch_size: int, device=None, *, resample: bool = False) -> "MimiDecodeStream":
         """A stateful tokens -> signal decoder for `batch_size` independent streams on `device` (default: the current cuda
         device).  Feed it with `push`; every push returns the samples of the frames it was given (include/audiocodecs_amd.h
-        ac_mimi_stream_decode*)."""
+        ac_mimi_stream_decode*).  `resample=True`: the samples come out at `sample_rate`, through a
+        `ResampleStream` behind the decoder (`finish` returns its tail)."""
         if self.mode == "encode":
             raise ValueError("decode_stream needs the decoder: this Mimi was built with mode=\"encode\"")
-        if self.sample_rate != self.config.sampling_rate:
+        if self.sample_rate != self.config.sampling_rate and not resample:
             raise ValueError(
-                f"decode_stream runs at the codec's own rate ({self.config.sampling_rate} Hz) only: streaming resampling is not "
-                f"supported (sample_rate={self.sample_rate})"
+                f"decode_stream runs at the codec's own rate ({self.config.sampling_rate} Hz): streaming resampling from or to "
+                f"sample_rate={self.sample_rate} is opt-in, pass resample=True"
             )
         if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
             raise ValueError(f"`batch_size` ({batch_size!r}) must be a positive int")
         self._check_num_codebooks()
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return MimiDecodeStream(self, self._native_for(torch.empty(0, device=dev)), batch_size)
+        return MimiDecodeStream(self, self._native_for(torch.empty(0, device=dev)), batch_size, bool(resample))
 
     # ---- measurement hook used by bench.py ------------------------------------------------------
     def profile_kernels(self, fn):
@@ -283,22 +286,41 @@ class Mimi(Codec):
         return [(buf[i].name.decode(), buf[i].launches, buf[i].total_ms, buf[i].flops, buf[i].bytes) for i in range(n)]
 
 
+def _boundary_resampler(codec, kind: str, batch_size: int, device, resample: bool):
+    """resample=True at another rate than the codec's: the boundary's resampler, in front of the encoder or behind the decoder."""
+    rate, own = int(codec.sample_rate), int(codec.config.sampling_rate)
+    if not resample or rate == own:
+        return None
+    return ResampleStream(rate, own, batch_size, device) if kind == "encode" else ResampleStream(own, rate, batch_size, device)
+
+
+_SHARED_PHASE = ("the slots of a resampling stream share one phase: a slot restarted alone would emit a different number of samples per "
+                 "push than its neighbours (`streams` must be None)")
+
+
 class MimiEncodeStream:
     """Streaming Mimi encode of `batch_size` streams (Mimi.encode_stream).  `push(sig)` takes [B, L] fp32 samples on the codec's
     device, any L >= 0, and returns the int64 tokens [B, n, K] of the n frames completed so far (n may be 0); a partial frame
     waits here until a later push completes it (`pending` samples, always below hop).  The tokens of a stream do not depend on
     how its signal was split into pushes, nor on the other streams.  The stream state and the workspace are device tensors owned
-    by this object."""
+    by this object.
+
+    With `resample=True` on a codec whose `sample_rate` is not the model's, `push` takes samples at `sample_rate`; they pass a
+    `ResampleStream` (0.5 ms of added latency for 16 -> 24 kHz) and frames then count resampled samples.  `finish()` flushes the
+    resampler's tail into the encoder and returns the tokens of any frame that completes; a trailing partial frame stays `pending`.
+    After `finish` only `reset` is accepted, and single slots cannot be reset (they share the resampler's phase)."""
 
     MAX_POSITIONS = 1 << 24     # transformer positions per stream (fp32 RoPE angle)
 
-    def __init__(self, codec: Mimi, nat: _NativeMimi, batch_size: int):
+    def __init__(self, codec: Mimi, nat: _NativeMimi, batch_size: int, resample: bool = False):
         self.codec = codec
         self._nat = nat
         self.batch_size = B = batch_size
         self.num_codebooks = codec.num_codebooks
         self.hop = codec.config.hop_length
         self.device = nat.device
+        self._rs = _boundary_resampler(codec, "encode", B, self.device, resample)
+        self._finished = False
         nbytes = nat.lib.ac_mimi_stream_state_bytes(nat.h, B)
         if nbytes == 0:
             raise _native.NativeError("ac_mimi_stream_state_bytes returned 0")
@@ -324,6 +346,8 @@ class MimiEncodeStream:
         nat, B = self._nat, self.batch_size
         mask = None
         if streams is not None:
+            if self._rs is not None:
+                raise ValueError(_SHARED_PHASE)
             idx = [streams] if isinstance(streams, int) else list(streams)
             if any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < B for i in idx):
                 raise ValueError(f"`streams` ({streams!r}) must list slots in [0, {B})")
@@ -337,6 +361,9 @@ class MimiEncodeStream:
         else:
             self._pending = self._pending[:, :0]
             self._frames = [0] * B
+            self._finished = False
+            if self._rs is not None:
+                self._rs.reset()
         with torch.cuda.device(self.device):
             self._call(nat.lib.ac_mimi_stream_reset(nat.h, _ptr(self._state), self._state.numel(), B, _ptr(mask), _stream()),
                        "ac_mimi_stream_reset")
@@ -350,6 +377,37 @@ class MimiEncodeStream:
             raise ValueError(f"push expects float32 samples, got {sig.dtype}")
         if sig.device != self.device:
             raise ValueError(f"push expects samples on {self.device}, got {sig.device}")
+        if self._finished:
+            raise ValueError("push after finish: the stream is closed (call reset() first)")
+        return self._take(self._resampled(sig, False) if self._rs is not None else sig)
+
+    @torch.no_grad()
+    def finish(self) -> torch.Tensor:
+        """Close the streams: the resampler's tail goes through the encoder; returns the tokens [B, n, K] of the frames it completes."""
+        if self._finished:
+            raise ValueError("finish after finish: the stream is closed (call reset() first)")
+        toks = self._take(self._resampled(None, True) if self._rs is not None
+                          else torch.empty(self.batch_size, 0, dtype=torch.float32, device=self.device))
+        self._finished = True
+        return toks
+
+    def _resampled(self, sig, finish: bool) -> torch.Tensor:
+        """The pending samples with the resampler's output for this push written straight behind them (one buffer, no second copy)."""
+        rs, pend = self._rs, self.pending
+        m = rs.out_len(0 if finish else sig.shape[1], finish)
+        whole = torch.empty(self.batch_size, pend + m, dtype=torch.float32, device=self.device)
+        if pend:
+            whole[:, :pend].copy_(self._pending)
+        if finish:
+            rs.finish(out=whole[:, pend:])
+        else:
+            rs.push(sig, out=whole[:, pend:])
+        self._pending = self._pending[:, :0]
+        return whole
+
+    def _take(self, sig: torch.Tensor) -> torch.Tensor:
+        """Samples at the codec's rate: run the frames they complete, keep the rest pending."""
+        B, hop, K = self.batch_size, self.hop, self.num_codebooks
         total = self.pending + sig.shape[1]
         n = total // hop
         if n == 0:
@@ -377,11 +435,16 @@ class MimiDecodeStream:
     """Streaming Mimi decode of `batch_size` streams (Mimi.decode_stream).  `push(toks)` takes [B, F, K] int64 tokens on the codec's
     device, K = the codec's `num_codebooks`, any F >= 0, and returns the [B, F * hop] fp32 samples of those frames at the codec's own
     rate.  The samples of a stream are those `toks_to_sig` gives on the stream's whole token sequence, for any number of frames, and
-    do not depend on the other streams.  The stream state and the workspace are device tensors owned by this object."""
+    do not depend on the other streams.  The stream state and the workspace are device tensors owned by this object.
+
+    With `resample=True` on a codec whose `sample_rate` is not the model's, the samples pass a `ResampleStream` to `sample_rate` on
+    their way out: a push returns what the resampler has completed (the count varies), `finish()` its tail, and everything together
+    has the length `toks_to_sig` returns.  After `finish` only `reset` is accepted, and single slots cannot be reset (they share the
+    resampler's phase)."""
 
     MAX_POSITIONS = 1 << 24     # transformer positions per stream (fp32 RoPE angle)
 
-    def __init__(self, codec: Mimi, nat: _NativeMimi, batch_size: int):
+    def __init__(self, codec: Mimi, nat: _NativeMimi, batch_size: int, resample: bool = False):
         self.codec = codec
         self._nat = nat
         self.batch_size = B = batch_size
@@ -389,6 +452,8 @@ class MimiDecodeStream:
         self.hop = codec.config.hop_length
         self._stride = codec.config.resample_stride
         self.device = nat.device
+        self._rs = _boundary_resampler(codec, "decode", B, self.device, resample)
+        self._finished = False
         nbytes = nat.lib.ac_mimi_stream_decode_state_bytes(nat.h, B)
         if nbytes == 0:
             raise _native.NativeError("ac_mimi_stream_decode_state_bytes returned 0")
@@ -408,6 +473,8 @@ class MimiDecodeStream:
         nat, B = self._nat, self.batch_size
         mask = None
         if streams is not None:
+            if self._rs is not None:
+                raise ValueError(_SHARED_PHASE)
             idx = [streams] if isinstance(streams, int) and not isinstance(streams, bool) else list(streams)
             if any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < B for i in idx):
                 raise ValueError(f"`streams` ({streams!r}) must list slots in [0, {B})")
@@ -419,6 +486,9 @@ class MimiDecodeStream:
                        "ac_mimi_stream_decode_reset")
         if streams is None:
             self._frames = [0] * B
+            self._finished = False
+            if self._rs is not None:
+                self._rs.reset()
         else:
             for i in idx:
                 self._frames[i] = 0
@@ -432,6 +502,23 @@ class MimiDecodeStream:
             raise ValueError(f"push expects int64 tokens, got {toks.dtype}")
         if toks.device != self.device:
             raise ValueError(f"push expects tokens on {self.device}, got {toks.device}")
+        if self._finished:
+            raise ValueError("push after finish: the stream is closed (call reset() first)")
+        sig = self._decode(toks)
+        return self._rs.push(sig) if self._rs is not None else sig
+
+    @torch.no_grad()
+    def finish(self) -> torch.Tensor:
+        """Close the streams: the resampler's tail [B, m] (nothing without one)."""
+        if self._finished:
+            raise ValueError("finish after finish: the stream is closed (call reset() first)")
+        self._finished = True
+        if self._rs is not None:
+            return self._rs.finish()
+        return torch.empty(self.batch_size, 0, dtype=torch.float32, device=self.device)
+
+    def _decode(self, toks: torch.Tensor) -> torch.Tensor:
+        B, hop, K = self.batch_size, self.hop, self.num_codebooks
         F = toks.shape[1]
         if F == 0:
             return torch.empty(B, 0, dtype=torch.float32, device=self.device)

@@ -7,6 +7,10 @@ the filter bank below restates its published algorithm --
 torchaudio is unpinned**; tests check it against an fp64 restatement and against the analytic
 response on band-limited tones.  Equal rates return the input unchanged, as torchaudio does.
 The FIR itself runs in the HIP library (``ac_resample``); there is no CPU fallback.
+
+``ResampleStream`` is the same conversion push by push (``ac_resample_stream_*``): it carries its filter
+history and its phase on the device, and the concatenation of what it returns is bit for bit what ``resample`` gives on the whole
+signal.  The codec streams use it for callers at another rate than the codec's (``encode_stream(..., resample=True)``).
 """
 
 from __future__ import annotations
@@ -17,7 +21,7 @@ from typing import Dict, Tuple
 
 import torch
 
-__all__ = ["resample", "sinc_kernel"]
+__all__ = ["resample", "sinc_kernel", "ResampleStream", "stream_out_len"]
 
 _LOWPASS_FILTER_WIDTH = 6
 _ROLLOFF = 0.99
@@ -70,3 +74,141 @@ def resample(sig: torch.Tensor, orig_freq, new_freq) -> torch.Tensor:
         )
     _native.check(rc, None, "ac_resample")
     return y
+
+
+def stream_out_len(consumed: int, L: int, n: int, o: int, width: int, finish: bool = False) -> int:
+    """Samples per stream that a push of L samples emits on a stream that has consumed `consumed` (with `finish`: that push as the
+    closing one).  Pure host arithmetic in the library (``ac_resample_stream_out_len``); needs no GPU."""
+    from . import _native
+
+    m = _native.lib().ac_resample_stream_out_len(int(consumed), int(L), int(n), int(o), int(width), int(bool(finish)))
+    if m < 0:
+        raise ValueError(f"stream_out_len: bad arguments (consumed={consumed}, L={L}, n={n}, o={o}, width={width})")
+    return int(m)
+
+
+def _positive_int(name, v) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"`{name}` ({v!r}) must be a positive int")
+    return v
+
+
+class ResampleStream:
+    """Streaming sample-rate conversion of `batch_size` streams that share one phase: `push(sig)` takes [B, L] fp32 samples at
+    `orig_freq`, any L >= 0, and returns the [B, m] samples at `new_freq` that no later input can change -- m varies from push to push
+    and may be 0; `finish()` takes all later input as silence and returns the rest, after which only `reset()` is accepted.  The
+    concatenated output is bit for bit `resample(whole signal)`, however the signal was split.  Output lags input by
+    `latency_samples` = width + o - 1 input samples (0.5 ms for 16 <-> 24 kHz).  Equal rates pass the input through.  The state is a
+    device tensor owned by this object; every call runs on the current stream and neither allocates in the library nor synchronises."""
+
+    def __init__(self, orig_freq: int, new_freq: int, batch_size: int, device=None):
+        self.orig_freq, self.new_freq = _positive_int("orig_freq", orig_freq), _positive_int("new_freq", new_freq)
+        self.batch_size = _positive_int("batch_size", batch_size)
+        self.identity = self.orig_freq == self.new_freq
+        self.consumed = 0        # input samples taken since the reset (the same for every slot)
+        self.emitted = 0         # output samples returned since the reset
+        self._finished = False
+        if self.identity:
+            self.device = None if device is None else torch.device(device)
+            self.n = self.o = 1
+            self.width = self.taps = 0
+            return
+        from . import _native
+
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise _native.NativeError("audiocodecs_amd.ResampleStream runs on MI355X only: give it a cuda device")
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        kern, self.n, self.o, self.width = sinc_kernel(self.orig_freq, self.new_freq)
+        self.taps = int(kern.shape[1])
+        self._lib = _native.lib()
+        nbytes = self._lib.ac_resample_stream_state_bytes(self.batch_size, self.taps)
+        if nbytes == 0:
+            raise _native.NativeError(f"ac_resample_stream_state_bytes returned 0 (B={self.batch_size}, taps={self.taps})")
+        self._kern = kern.to(self.device)
+        self._state_buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self._state_buf.data_ptr()) % 256
+        self._state = self._state_buf[off:off + nbytes]
+        self.reset()
+
+    @property
+    def latency_samples(self) -> int:
+        """Input samples that must follow a sample before the outputs it bears on are complete."""
+        return 0 if self.identity else self.width + self.o - 1
+
+    def out_len(self, L: int, finish: bool = False) -> int:
+        """Samples per stream the next `push` of L samples (`finish=True`: that push as the closing one) returns."""
+        if self.identity:
+            return int(L)
+        return stream_out_len(self.consumed, L, self.n, self.o, self.width, finish)
+
+    @torch.no_grad()
+    def reset(self) -> None:
+        """Start all streams afresh."""
+        self.consumed = self.emitted = 0
+        self._finished = False
+        if self.identity:
+            return
+        from . import _native
+
+        with torch.cuda.device(self.device):
+            rc = self._lib.ac_resample_stream_reset(C.c_void_p(self._state.data_ptr()), self._state.numel(), self.batch_size, self.n, self.o,
+                                                    self.taps, self.width, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, None, "ac_resample_stream_reset")
+
+    def _run(self, x, L: int, finish: bool, out):
+        from . import _native
+
+        B = self.batch_size
+        m = self.out_len(L, finish)
+        if out is None:
+            out = torch.empty(B, m, dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape != (B, m) or out.dtype != torch.float32 or out.device != self.device
+              or (m and out.stride(1) != 1) or (m and B > 1 and out.stride(0) < m)):
+            raise ValueError(f"`out` must be a [{B}, {m}] float32 tensor on {self.device} with unit stride along its rows")
+        if L or finish:
+            if L and (x.stride(1) != 1 or (B > 1 and x.stride(0) < L)):
+                x = x.contiguous()
+            with torch.cuda.device(self.device):
+                rc = self._lib.ac_resample_stream_push(
+                    C.c_void_p(self._state.data_ptr()), self._state.numel(), C.c_void_p(x.data_ptr() if L else 0), max(x.stride(0), L) if L else 0, B, L,
+                    self.consumed, C.c_void_p(self._kern.data_ptr()), self.n, self.o, self.taps, self.width,
+                    C.c_void_p(out.data_ptr() if m else 0), max(out.stride(0), m), m, int(finish), C.c_void_p(torch.cuda.current_stream().cuda_stream),
+                )
+            _native.check(rc, None, "ac_resample_stream_push")
+        self.consumed += L
+        self.emitted += m
+        self._finished = finish
+        return out
+
+    @torch.no_grad()
+    def push(self, sig: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """sig [B, L] fp32 -> [B, m].  `out`: where to write them -- a [B, out_len(L)] fp32 tensor whose rows may be further apart than
+        they are long (a column slice of a larger buffer: the samples land straight behind those the caller already holds)."""
+        B = self.batch_size
+        if not isinstance(sig, torch.Tensor) or sig.dim() != 2 or sig.shape[0] != B:
+            raise ValueError(f"push expects a [{B}, L] tensor, got {tuple(sig.shape) if isinstance(sig, torch.Tensor) else type(sig)}")
+        if sig.dtype != torch.float32:
+            raise ValueError(f"push expects float32 samples, got {sig.dtype}")
+        if self._finished:
+            raise ValueError("push after finish: the stream is closed (call reset() first)")
+        if self.identity:
+            self.consumed += sig.shape[1]
+            self.emitted += sig.shape[1]
+            if out is not None:
+                out.copy_(sig)
+                return out
+            return sig
+        if sig.device != self.device:
+            raise ValueError(f"push expects samples on {self.device}, got {sig.device}")
+        return self._run(sig, int(sig.shape[1]), False, out)
+
+    @torch.no_grad()
+    def finish(self, out: torch.Tensor = None) -> torch.Tensor:
+        """Close the streams: what `resample` on the whole signal still has beyond the samples returned so far, [B, m]."""
+        if self._finished:
+            raise ValueError("finish after finish: the stream is closed (call reset() first)")
+        if self.identity:
+            self._finished = True
+            return torch.empty(self.batch_size, 0, dtype=torch.float32, device=self.device) if out is None else out
+        return self._run(None, 0, True, out)

@@ -365,6 +365,36 @@ int ac_embs_projected(ac_handle* h, int K, float* embs_dev, void* stream);
 int ac_resample(const float* x_dev, int B, int L, const float* kern_dev, int n, int o, int taps, int width,
                 float* y_dev, int L_out, void* stream);
 
+/* The same conversion push by push, for streams: B streams share one rate pair and one phase; each push brings L
+ * samples per stream and returns the outputs that no later input can change.  With taps = 2 * width + o, output group i (outputs
+ * i*n .. i*n + n - 1) reads the inputs i*o - width .. i*o - width + taps - 1 and is complete once width + o + i*o samples are in: after
+ * `total` samples G(total) = total < width + o ? 0 : (total - width - o) / o + 1 groups are.  A push emits the groups
+ * G(consumed) .. G(consumed + L) - 1, i.e. n * (G(after) - G(before)) samples -- possibly none, and not the same number every push.  A
+ * push with finish != 0 takes all later input as zero and emits the rest, up to ceil(n * total / o) outputs in all: ac_resample's
+ * length, and, concatenated, ac_resample's values bit for bit (the same fp32 chain per output, ascending taps).  The added latency is
+ * width + o - 1 input samples (0.5 ms for 16 <-> 24 kHz).
+ *
+ * Handle-free.  The caller owns the state: ac_resample_stream_state_bytes(B, taps) bytes of device memory, 256-byte aligned, holding a
+ * header (a magic of its own, B, n, o, taps, width), the samples consumed per stream and the last taps - 1 input samples per stream
+ * (zeros on a fresh stream).  The caller also keeps the count of samples consumed since the reset and passes it to every push
+ * (ac_resample_stream_out_len needs it to size the output before the launch); the device compares it, and the geometry, with the state
+ * and writes NaN instead of samples when they disagree (a state never reset, reset for another geometry, pushed after its finish, or a
+ * count that is not the state's).  ac_resample_stream_out_len is pure host arithmetic: the number of samples per stream a push of L
+ * samples (or that push as the closing one) emits; AC_EINVAL (-1) for a negative or overflowing argument.
+ * ac_resample_stream_push reads x_dev [B] rows of L samples x_pitch floats apart and writes y_dev [B] rows y_pitch floats apart, of
+ * which y_capacity floats per row are the caller's to write: with the pitch a caller can have the samples written straight behind
+ * those it already holds.  AC_EINVAL for a null or misaligned state, geometry that is not a filter bank's (taps != 2 * width + o,
+ * taps > 8192, B, n, o < 1), a negative L or count, or a pitch shorter than its row; AC_ENOMEM for a state shorter than
+ * ac_resample_stream_state_bytes or y_capacity below the push's output length: all decided on the host before anything is launched,
+ * and the state stays as it was.  A push is two launches on the caller's stream (one when it emits nothing, none for L == 0 without
+ * finish); nothing allocates or synchronises.  After the closing push only a reset makes the state usable again. */
+long long ac_resample_stream_out_len(long long consumed, int L, int n, int o, int width, int finish);
+size_t ac_resample_stream_state_bytes(int B, int taps);
+int ac_resample_stream_reset(void* state_dev, size_t state_bytes, int B, int n, int o, int taps, int width, void* stream);
+int ac_resample_stream_push(void* state_dev, size_t state_bytes, const float* x_dev, long long x_pitch, int B, int L, long long consumed,
+                            const float* kern_dev, int n, int o, int taps, int width, float* y_dev, long long y_pitch, long long y_capacity,
+                            int finish, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */

@@ -4,6 +4,7 @@ seeded synthetic weights, noise input / random tokens.
 
     python tools/encodec_stream_latency.py --batch 1 --frames 1 [--pushes 200 --warmup 20] [--direction decode]
     python tools/encodec_stream_latency.py --sweep [--out profiles/encodec_stream_latency.json]
+    python tools/encodec_stream_latency.py --sweep --sample-rate 16000 --out profiles/encodec_stream_latency_16k.json
 
 Same method as tools/mimi_stream_latency.py: after the stream's own start-up hold (one push of WARMUP_FRAMES frames, not timed) and
 `--warmup` untimed pushes, every push is timed on the host from `push` to a stream synchronisation (what a caller waiting for its
@@ -11,7 +12,13 @@ tokens sees).  Prints one JSON line per configuration: median / p99 push latency
 compute second, per stream and batch-wide), the per-kernel split of ONE further push (Encodec.profile_kernels: HIP-event time per
 kernel name, launches) and, for scale, the one-shot time of a 10 s clip at the same batch size (`sig_to_toks` / `toks_to_sig`, median
 of 5): what a caller without streaming pays for every new frame.  `--sweep` runs B = 1 / 8 / 64 with one-frame and 25-frame pushes
-in both directions; `--out` also writes the lines as one JSON list."""
+in both directions; `--out` also writes the lines as one JSON list.
+
+`--sample-rate R` (R != 24000) measures the caller at another rate: every configuration runs twice in the same process, as the plain
+24 kHz stream ("resample": false) and as `encode_stream / decode_stream(B, resample=True)` of a codec built for rate R ("resample":
+true), whose pushes carry the same audio time (F frames; at 16 kHz an encode push is 213 or 214 samples per frame) and pass the
+stateful resampler (ResampleStream: two launches per push, not on a handle, so not in the per-kernel split).  The difference of the
+two medians is the resampler's cost per push."""
 import argparse
 import json
 import os
@@ -39,21 +46,24 @@ def timed(fn, reps):
     return float(np.median(out))
 
 
-def measure(codec, direction, B, F, pushes, warmup):
+def measure(codec, direction, B, F, pushes, warmup, resample=False):
     cfg = codec.config
     hop, K = cfg.hop_length, codec.num_codebooks
-    s = codec.encode_stream(B) if direction == "encode" else codec.decode_stream(B)
-    W = s.WARMUP_FRAMES
+    s = codec.encode_stream(B, resample=resample) if direction == "encode" else codec.decode_stream(B, resample=resample)
+    rate = int(codec.sample_rate)                    # the caller's rate: the codec's own unless resampling
+    W = s.WARMUP_FRAMES + (1 if resample else 0)     # (resampling: one frame more, the resampler holds the last 0.5 ms back)
     total = warmup + pushes + 1                      # + 1: the profiled push
     frames = W + total * F
     if direction == "encode":
-        data = torch.from_numpy((prng.normal(11, "stream_latency", (B, frames * hop)) * 0.1).astype(np.float32)).cuda()
-        piece = lambda a, n: data[:, a * hop:(a + n) * hop]      # noqa: E731
+        at = lambda a: (a * hop * rate + cfg.sampling_rate // 2) // cfg.sampling_rate       # noqa: E731  (frame a's first sample at `rate`)
+        data = torch.from_numpy((prng.normal(11, "stream_latency", (B, at(frames))) * 0.1).astype(np.float32)).cuda()
+        piece = lambda a, n: data[:, at(a):at(a + n)]            # noqa: E731
     else:
         data = torch.from_numpy(prng.randint(11, "stream_latency", (B, frames, K), cfg.codebook_size)).to(torch.int64).cuda()
         piece = lambda a, n: data[:, a:a + n]                    # noqa: E731
     first = s.push(piece(0, W))                      # the start-up hold, released as one push
-    assert first.shape[1] == (W if direction == "encode" else W * hop)
+    assert resample or first.shape[1] == (W if direction == "encode" else W * hop)
+    assert first.shape[1] > 0
     torch.cuda.synchronize()
     lat = []
     for i in range(warmup + pushes):
@@ -62,7 +72,7 @@ def measure(codec, direction, B, F, pushes, warmup):
         torch.cuda.synchronize()
         if i >= warmup:
             lat.append(time.perf_counter() - t0)
-    assert out.shape[1] == (F if direction == "encode" else F * hop)
+    assert resample or out.shape[1] == (F if direction == "encode" else F * hop)
     stats = codec.profile_kernels(lambda: s.push(piece(W + (warmup + pushes) * F, F)))
     lat = np.array(lat) * 1e3
     med = float(np.median(lat))
@@ -70,7 +80,7 @@ def measure(codec, direction, B, F, pushes, warmup):
     # the one-shot path on a 10 s clip at the same batch size
     n10 = 10 * cfg.sampling_rate // hop
     if direction == "encode":
-        clip = torch.from_numpy((prng.normal(12, "stream_latency", (B, n10 * hop)) * 0.1).astype(np.float32)).cuda()
+        clip = torch.from_numpy((prng.normal(12, "stream_latency", (B, n10 * hop * rate // cfg.sampling_rate)) * 0.1).astype(np.float32)).cuda()
         one_shot = lambda: codec.sig_to_toks(clip)               # noqa: E731
     else:
         clip = torch.from_numpy(prng.randint(12, "stream_latency", (B, n10, K), cfg.codebook_size)).to(torch.int64).cuda()
@@ -95,15 +105,23 @@ def main():
     ap.add_argument("--direction", default="encode", choices=["encode", "decode"])
     ap.add_argument("--sweep", action="store_true", help="B = 1 / 8 / 64 x 1 / 25 frames per push x both directions")
     ap.add_argument("--out", default=None, help="also write the result lines to this file as one JSON list")
+    ap.add_argument("--sample-rate", type=int, default=24000, help="the caller's rate; another one than 24000 also runs every configuration with resample=True")
     a = ap.parse_args()
     cfg = ENCODEC_24KHZ
-    codec = Encodec(24000, num_codebooks=8, state_dict=checkpoint.synthetic_state_dict(cfg, seed=0), config=cfg, precision=a.precision).eval()
+    sd = checkpoint.synthetic_state_dict(cfg, seed=0)
+    codec = Encodec(24000, num_codebooks=8, state_dict=sd, config=cfg, precision=a.precision).eval()
     runs = [(d, B, F) for d in ("encode", "decode") for B in (1, 8, 64) for F in (1, 25)] if a.sweep else [(a.direction, a.batch, a.frames)]
+    variants = [(codec, False)]
+    if a.sample_rate != cfg.sampling_rate:
+        variants.append((Encodec(a.sample_rate, num_codebooks=8, state_dict=sd, config=cfg, precision=a.precision).eval(), True))
     rows = []
     for d, B, F in runs:
-        rows.append(measure(codec, d, B, F, a.pushes, a.warmup))
-        rows[-1]["precision"] = a.precision or "default"
-        print(json.dumps(rows[-1]), flush=True)
+        for c, rs in variants:
+            rows.append(measure(c, d, B, F, a.pushes, a.warmup, rs))
+            rows[-1]["precision"] = a.precision or "default"
+            if len(variants) > 1:
+                rows[-1].update(sample_rate=int(c.sample_rate), resample=rs)
+            print(json.dumps(rows[-1]), flush=True)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(rows, f, indent=1)
