@@ -171,6 +171,10 @@ EXPORTS = {
     "ac_encodec_stream_decode_reset": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
     "ac_encodec_stream_decode_workspace_bytes": (_sz, [_vp, _i, _i]),
     "ac_encodec_stream_decode": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ac_encodec_stream_reset_slots": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _vp]),
+    "ac_encodec_stream_decode_reset_slots": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _vp]),
+    "ac_encodec_stream_encode_slots": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "ac_encodec_stream_decode_slots": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "ac_embs": (_i, [_vp, _i, _vp, _vp]),
     "ac_embs_projected": (_i, [_vp, _i, _vp, _vp]),
     "ac_resample": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -223,7 +223,10 @@ struct ac_handle {
     std::map<size_t, size_t> winv_of;   // split16 images: float offset of a packed fp32 matrix -> offset of its per-row 2^-s
     std::map<const void*, int> mimi_streams;   // mimi_stream.hip: state buffers ac_mimi_stream_reset prepared on this handle -> their B
     std::map<const void*, int> mimi_dstreams;  //   the same for decode states (ac_mimi_stream_decode_reset); an address is in at most one of the two
-    struct EStreamReg { int B; bool fresh; };  // encodec_stream.hip: `fresh`: no push since the reset (the next one must bring the warm-up frames)
+    struct EStreamReg {                        // encodec_stream.hip
+        int B;
+        std::vector<uint8_t> fresh;            //   [B]: no push on that slot since its reset (its next one must bring the warm-up frames)
+    };
     std::map<const void*, EStreamReg> encodec_streams, encodec_dstreams;   //   states ac_encodec_stream_reset / _decode_reset prepared on this handle
     // amax slots (split16.h): [slot][amax_B] words, handed out in launch order, cleared at the start of every pass
     unsigned* amax_buf = nullptr;

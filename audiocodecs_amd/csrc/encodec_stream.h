@@ -15,11 +15,17 @@
 // The epilogue (thread = (stream, unit)) applies the non-linearities (lstm.h sigmoidf_ / tanhf_), updates c IN PLACE in the stream state,
 // writes h[t] to the push's h sequence (the next step's and the next layer's operand) and, on the push's last step, to the state;
 // the last layer also writes ELU(h[t] + x[t]), the module's skip connection in the flavour the following conv reads.
+//
+// A slot push (ac_encodec_stream_encode_slots / _decode_slots) runs n of the state's streams: every buffer of the push is dense [n], and
+// the step kernel reaches the state's c and h rows through the slot map of stream_stage.h (mstream_slot).  Two small kernels go with it:
+//   estream_gather_h_kernel     the carried h of the listed streams [L][cap][D] -> the push's dense copy [L][n][D]
+//   estream_reset_slots_kernel  position = 0, fresh = 1, h = c = 0 for the listed streams and nothing else
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "lstm.h"
 #include "tap_gemm.h"
+#include "stream_stage.h"
 
 constexpr unsigned ESTREAM_MAGIC = 0x54534345u;   // "ECST"
 constexpr unsigned EDSTREAM_MAGIC = 0x54534445u;  // "EDST": a decode state (its own layout; never accepted where an encode state is expected)
@@ -36,6 +42,8 @@ struct EStreamLstmParams {
     float* yelu;                 // last layer: ELU(h[t] + x[t]) of stream b at yelu + b * y_bs
     long long gin_bs, hprev_bs, hout_bs, skip_bs, y_bs;
     int B, D;
+    const int* slot;             // null, or [B] (device): row b's c and hstate rows are those of stream slot[b] of the `cap` the state holds
+    int cap;
 };
 
 template <int KPW>   // k-steps per wave: D = 64 * KPW
@@ -52,7 +60,8 @@ __global__ __launch_bounds__(256) void estream_lstm_step_kernel(const EStreamLst
     float gi[4], c_old, sk = 0.f;
 #pragma unroll
     for (int g = 0; g < 4; ++g) gi[g] = __fadd_rn(p.gin[eb * p.gin_bs + g * D + unit], p.bias[g * D + unit]);
-    c_old = p.c[eb * D + unit];
+    const long long es = mstream_slot(p.slot, (int)eb, p.cap);       // the row of the state's c and h (-1: none, the row touches no state)
+    c_old = es >= 0 ? p.c[es * D + unit] : 0.f;
     if (p.skip) sk = p.skip[eb * p.skip_bs + unit];
 
     ac::f32x4 w[KPW];
@@ -95,8 +104,45 @@ __global__ __launch_bounds__(256) void estream_lstm_step_kernel(const EStreamLst
     const float ig = ac::sigmoidf_(pre[0]), fg = ac::sigmoidf_(pre[1]), gg = ac::tanhf_(pre[2]), og = ac::sigmoidf_(pre[3]);
     const float cn = __fadd_rn(__fmul_rn(fg, c_old), __fmul_rn(ig, gg));
     const float hn = __fmul_rn(og, ac::tanhf_(cn));
-    p.c[eb * D + unit] = cn;
+    if (es >= 0) p.c[es * D + unit] = cn;
     p.hout[eb * p.hout_bs + unit] = hn;
-    if (p.hstate) p.hstate[eb * D + unit] = hn;
+    if (p.hstate && es >= 0) p.hstate[es * D + unit] = hn;
     if (p.skip) p.yelu[eb * p.y_bs + unit] = ac::elu1(__fadd_rn(hn, sk));
+}
+
+// dst [L][n][D] = hstate [L][cap][D] rows slot[0 .. n): the dense copy of the carried h that step 0 of a slot push reads (the lockstep
+// push takes it with one memcpy).  One thread per 16 bytes; a row whose map entry is outside [0, cap) reads nothing and gets zeros.
+template <int U = 0>
+__global__ __launch_bounds__(256) void estream_gather_h_kernel(const float* hstate, float* dst, const int* slot, int n, int cap, int L, int D) {
+    const int D4 = D / 4;
+    const long long total = (long long)L * n * D4;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int d = (int)(e % D4);
+        const long long lb = e / D4;
+        const int b = (int)(lb % n), l = (int)(lb / n);
+        const int sb = mstream_slot(slot, b, cap);
+        ac::f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (sb >= 0) v = reinterpret_cast<const ac::f32x4*>(hstate + ((long long)l * cap + sb) * D)[d];
+        reinterpret_cast<ac::f32x4*>(dst + ((long long)l * n + b) * D)[d] = v;
+    }
+}
+
+// One workgroup per listed stream: position = 0, fresh = 1, and the stream's h and c rows of every layer = 0.  Nothing else is touched
+// (not the header, not the conv histories: a fresh stream's are rebuilt from its first push); an entry outside [0, cap) is skipped.
+template <int U = 0>
+__global__ __launch_bounds__(256) void estream_reset_slots_kernel(long long* pos, int* fresh, float* hstate, float* cstate, const int* slot, int n, int cap,
+                                                                  int L, int D) {
+    const int b = blockIdx.x;
+    if (b >= n) return;
+    const int sb = mstream_slot(slot, b, cap);
+    if (sb < 0) return;
+    if (threadIdx.x == 0) {
+        pos[sb] = 0;
+        fresh[sb] = 1;
+    }
+    for (int e = threadIdx.x; e < L * D; e += 256) {
+        const long long o = ((long long)(e / D) * cap + sb) * D + e % D;
+        hstate[o] = 0.f;
+        cstate[o] = 0.f;
+    }
 }

@@ -23,11 +23,13 @@ struct EStreamLayout {
     std::vector<int> conv_P, conv_C;           //   rows (k - stride; 1 for a transposed conv) and channels of each
     size_t lstm_h = 0, lstm_c = 0, lstm_bytes = 0;   // lstm_bytes: h and c together (contiguous: one memset clears them)
     size_t total = 0;
+    int B = 0;                                 // streams the state holds
 };
 
 static EStreamLayout estream_layout(const ac_handle* h, int B, bool dec) {
     const ac_config& c = h->cfg;
     EStreamLayout L;
+    L.B = B;
     size_t off = align_up(sizeof(MStreamHeader), 256);
     auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
     L.pos = take((size_t)B * 8);
@@ -74,9 +76,10 @@ static unsigned long long estream_fingerprint(const ac_config& c) {
 // frames the first push after a reset must bring: the widest frame-rate conv (see the head of this file)
 static int warmup_frames(const ac_handle* h) { return std::max(h->cfg.kernel_size, h->cfg.last_kernel_size); }
 
-static int estream_stage(ac_handle* h, hipStream_t st, char* state, const EStreamLayout& Ls, int l, const Act& x, int B, float* staged, size_t cap, int mode) {
+// (`slot`, here and below: the slot map of a push that runs B listed streams of the state's Ls.B -- stream_stage.h; null = all, in order)
+static int estream_stage(ac_handle* h, hipStream_t st, char* state, const EStreamLayout& Ls, const int* slot, int l, const Act& x, int B, float* staged, size_t cap, int mode) {
     return stream_stage(h, st, reinterpret_cast<float*>(state + Ls.conv[l]), reinterpret_cast<const int*>(state + Ls.fresh), Ls.conv_P[l], Ls.conv_C[l], l, x, B,
-                        staged, cap, mode, true);
+                        staged, cap, mode, true, slot, Ls.B);
 }
 
 // Pushes of up to this many frames take the input projections of the LSTM through mstream_linear_kernel, longer ones through the
@@ -120,7 +123,7 @@ static int estream_lstm_proj(ac_handle* h, hipStream_t st, const PackedGemm& g, 
 }
 
 // x [B][F][D] -> ELU(lstm(x) + x) [B][F][D] at `yelu`, from the state's h / c, which it leaves at the push's last step
-static int estream_lstm(ac_handle* h, hipStream_t st, const LstmPlan& lp, const Act& x, char* state, const EStreamLayout& Ls, const LstmWs& ws,
+static int estream_lstm(ac_handle* h, hipStream_t st, const LstmPlan& lp, const Act& x, char* state, const EStreamLayout& Ls, const int* slot, const LstmWs& ws,
                         float* yelu, int B, int F, Act2* y) {
     const int D = lp.D, L = lp.layers;
     if (D % 64 != 0 || D > 512) return fail(h, AC_EINVAL, "LSTM width %d unsupported (need 64, 128, 256 or 512)", D);
@@ -128,8 +131,15 @@ static int estream_lstm(ac_handle* h, hipStream_t st, const LstmPlan& lp, const 
     float* hstate = reinterpret_cast<float*>(state + Ls.lstm_h);
     float* cstate = reinterpret_cast<float*>(state + Ls.lstm_c);
     // step 0 reads the carried h from a copy: the last step of a one-frame push rewrites the state's h while other workgroups still read it
+    // (a slot push gathers its streams' rows into the same dense [L][B][D] copy)
     float* h_in = ws.c;
-    HIPCHK(h, hipMemcpyAsync(h_in, hstate, (size_t)L * B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (!slot) {
+        HIPCHK(h, hipMemcpyAsync(h_in, hstate, (size_t)L * B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    } else {
+        ProfScope ps(h, st, "estream_gather_h_kernel", 0.0, 8.0 * L * B * D);
+        hipLaunchKernelGGL(estream_gather_h_kernel<>, dim3(grid_for((long long)L * B * (D / 4))), dim3(256), 0, st, hstate, h_in, slot, B, Ls.B, L, D);
+        HIPCHK(h, hipGetLastError());
+    }
     const long long FD = (long long)F * D;
     for (int l = 0; l < L; ++l) {
         const bool last = l == L - 1;
@@ -149,8 +159,10 @@ static int estream_lstm(ac_handle* h, hipStream_t st, const LstmPlan& lp, const 
             q.hprev_bs = t == 0 ? D : FD;
             q.hout = hseq + (long long)t * D;
             q.hout_bs = FD;
-            q.hstate = t == F - 1 ? hstate + (long long)l * B * D : nullptr;
-            q.c = cstate + (long long)l * B * D;
+            q.hstate = t == F - 1 ? hstate + (long long)l * Ls.B * D : nullptr;
+            q.c = cstate + (long long)l * Ls.B * D;
+            q.slot = slot;
+            q.cap = Ls.B;
             if (last) {
                 q.skip = x.p + (long long)t * x.ts;
                 q.skip_bs = x.bs;
@@ -177,11 +189,11 @@ static int estream_lstm(ac_handle* h, hipStream_t st, const LstmPlan& lp, const 
 }
 
 // residual block on [history | ELU(x)]: y = [ELU(conv_k3(ELU(x))) | x] [W1; Ws] + (b1 + bs), ELU'd (every consumer starts with ELU)
-static int estream_resblock(ac_handle* h, hipStream_t st, char* state, const EStreamLayout& Ls, int l, const ResBlockPlan& rb, const Act2& x, int B,
+static int estream_resblock(ac_handle* h, hipStream_t st, char* state, const EStreamLayout& Ls, const int* slot, int l, const ResBlockPlan& rb, const Act2& x, int B,
                             WsPtrs& ws, size_t cap, Act2* y) {
     const int L = x.raw.L, ch = rb.C;
     float* stg = ws.take();
-    int rc = estream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, STAGE_REFLECT);
+    int rc = estream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, STAGE_REFLECT);
     if (rc) return rc;
     float* hb = ws.take();
     Act2 hv;
@@ -209,33 +221,33 @@ static int estream_resblock(ac_handle* h, hipStream_t st, char* state, const ESt
     return AC_OK;
 }
 
-static void estream_advance(hipStream_t st, char* state, const EStreamLayout& Ls, int B, int F) {
+static void estream_advance(hipStream_t st, char* state, const EStreamLayout& Ls, const int* slot, int B, int F) {
     hipLaunchKernelGGL(mstream_advance_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
-                       reinterpret_cast<int*>(state + Ls.fresh), B, F);
+                       reinterpret_cast<int*>(state + Ls.fresh), B, F, slot, Ls.B);
 }
 
 // one push: sig [B][F*hop] -> feats [B][F][H]; the stream state advances by F frames (encoder_fwd on [history | chunk])
-static int estream_encoder(ac_handle* h, hipStream_t st, char* state, const EStreamLayout& Ls, const float* sig, int B, int F, float* feats,
+static int estream_encoder(ac_handle* h, hipStream_t st, char* state, const EStreamLayout& Ls, const int* slot, const float* sig, int B, int F, float* feats,
                            WsPtrs& ws, size_t cap) {
     const ac_config& c = h->cfg;
     const int T = F * h->hop;
     int l = 0, rc;
     Act2 x, y;
     float* stg = ws.take();
-    if ((rc = estream_stage(h, st, state, Ls, l, Act{sig, (long long)T, 1, T, 1}, B, stg, cap, STAGE_REFLECT))) return rc;
+    if ((rc = estream_stage(h, st, state, Ls, slot, l, Act{sig, (long long)T, 1, T, 1}, B, stg, cap, STAGE_REFLECT))) return rc;
     if ((rc = mstream_conv(h, st, h->enc_stem, staged_act(stg, B, T + Ls.conv_P[l], 1), c.kernel_size, 1, T, Out{ws.take(), ws.take()}, B, &x))) return rc;
     ws.give(stg);
     ++l;
     for (int i = 0; i < c.num_ratios; ++i) {
         const int ratio = c.upsampling_ratios[c.num_ratios - 1 - i];
-        if ((rc = estream_resblock(h, st, state, Ls, l, h->enc_rb[i], x, B, ws, cap, &y))) return rc;
+        if ((rc = estream_resblock(h, st, state, Ls, slot, l, h->enc_rb[i], x, B, ws, cap, &y))) return rc;
         ws.give(x);
         x = y;
         ++l;
         // down-sampler (k = 2 * ratio, stride ratio) on [history | ELU(x)]
         const int L = x.elu.L, ch = x.elu.C;
         stg = ws.take();
-        if ((rc = estream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, STAGE_REFLECT))) return rc;
+        if ((rc = estream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, STAGE_REFLECT))) return rc;
         ws.give(x);
         const bool last = i == c.num_ratios - 1;     // the last one feeds the LSTM: raw only
         if ((rc = mstream_conv(h, st, h->enc_down[i], staged_act(stg, B, L + Ls.conv_P[l], ch), 2 * ratio, ratio, L / ratio,
@@ -245,22 +257,22 @@ static int estream_encoder(ac_handle* h, hipStream_t st, char* state, const EStr
         ++l;
     }
     float* ye = ws.take();
-    if ((rc = estream_lstm(h, st, h->enc_lstm, x.raw, state, Ls, ws.lstm, ye, B, F, &y))) return rc;
+    if ((rc = estream_lstm(h, st, h->enc_lstm, x.raw, state, Ls, slot, ws.lstm, ye, B, F, &y))) return rc;
     ws.give(x);
     x = y;
     stg = ws.take();
-    if ((rc = estream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, STAGE_REFLECT))) return rc;
+    if ((rc = estream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, STAGE_REFLECT))) return rc;
     ws.give(x);
     if ((rc = mstream_conv(h, st, h->enc_final, staged_act(stg, B, F + Ls.conv_P[l], h->D), c.last_kernel_size, 1, F, Out{feats, nullptr}, B, nullptr))) return rc;
     ws.give(stg);
     capture(h, st, Act{feats, (long long)F * c.hidden_size, c.hidden_size, F, c.hidden_size}, B);   // test hook: the push's features
-    estream_advance(st, state, Ls, B, F);
+    estream_advance(st, state, Ls, slot, B, F);
     HIPCHK(h, hipGetLastError());
     return AC_OK;
 }
 
 // one push: toks [B][F][K] -> sig [B][F*hop]; the decode state advances by F frames (decoder_fwd on [history | chunk])
-static int estream_decoder(ac_handle* h, hipStream_t st, char* state, const EStreamLayout& Ls, const long long* toks, int B, int F, int K, float* sig,
+static int estream_decoder(ac_handle* h, hipStream_t st, char* state, const EStreamLayout& Ls, const int* slot, const long long* toks, int B, int F, int K, float* sig,
                            WsPtrs& ws, size_t cap) {
     const ac_config& c = h->cfg;
     const int H = c.hidden_size;
@@ -269,20 +281,20 @@ static int estream_decoder(ac_handle* h, hipStream_t st, char* state, const EStr
     if ((rc = rvq_decode_fwd(h, st, toks, B * F, K, zb))) return rc;
     Act2 x, y;
     float* stg = ws.take();
-    if ((rc = estream_stage(h, st, state, Ls, l, Act{zb, (long long)F * H, H, F, H}, B, stg, cap, STAGE_REFLECT))) return rc;
+    if ((rc = estream_stage(h, st, state, Ls, slot, l, Act{zb, (long long)F * H, H, F, H}, B, stg, cap, STAGE_REFLECT))) return rc;
     ws.give(zb);
     if ((rc = mstream_conv(h, st, h->dec_first, staged_act(stg, B, F + Ls.conv_P[l], H), c.kernel_size, 1, F, Out{ws.take(), nullptr}, B, &x))) return rc;
     ws.give(stg);
     ++l;
     float* ye = ws.take();
-    if ((rc = estream_lstm(h, st, h->dec_lstm, x.raw, state, Ls, ws.lstm, ye, B, F, &y))) return rc;
+    if ((rc = estream_lstm(h, st, h->dec_lstm, x.raw, state, Ls, slot, ws.lstm, ye, B, F, &y))) return rc;
     ws.give(x);
     x = y;
     for (int i = 0; i < c.num_ratios; ++i) {
         const int ratio = c.upsampling_ratios[i], cin = h->dec_up[i].Ktot / 2, cup = h->dec_up[i].N / ratio, L = x.elu.L;
         // transposed conv (k = 2 ratio): output row m = [x[m-1] | x[m]] Wp (convtr_fwd), x[-1] from the cache (zeros when fresh)
         stg = ws.take();
-        if ((rc = estream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, STAGE_ZERO))) return rc;
+        if ((rc = estream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, STAGE_ZERO))) return rc;
         ws.give(x);
         if ((rc = mstream_conv(h, st, h->dec_up[i], staged_act(stg, B, L + Ls.conv_P[l], cin), 2, 1, L, Out{ws.take(), ws.take()}, B, &y))) return rc;
         ws.give(stg);
@@ -290,18 +302,18 @@ static int estream_decoder(ac_handle* h, hipStream_t st, char* state, const EStr
         const int Lu = L * ratio;                      // [B][L][ratio * cup] is [B][L * ratio][cup]
         x.raw = Act{y.raw.p, (long long)Lu * cup, cup, Lu, cup, y.raw.amax, y.raw.amax_n};
         x.elu = Act{y.elu.p, (long long)Lu * cup, cup, Lu, cup, y.elu.amax, y.elu.amax_n};
-        if ((rc = estream_resblock(h, st, state, Ls, l, h->dec_rb[i], x, B, ws, cap, &y))) return rc;
+        if ((rc = estream_resblock(h, st, state, Ls, slot, l, h->dec_rb[i], x, B, ws, cap, &y))) return rc;
         ws.give(x);
         x = y;
         ++l;
     }
     const int Ts = x.elu.L, Fh = x.elu.C;
     stg = ws.take();
-    if ((rc = estream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, STAGE_REFLECT))) return rc;
+    if ((rc = estream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, STAGE_REFLECT))) return rc;
     ws.give(x);
     if ((rc = mstream_conv(h, st, h->dec_head, staged_act(stg, B, Ts + Ls.conv_P[l], Fh), c.last_kernel_size, 1, Ts, Out{sig, nullptr}, B, nullptr))) return rc;
     ws.give(stg);
-    estream_advance(st, state, Ls, B, F);
+    estream_advance(st, state, Ls, slot, B, F);
     HIPCHK(h, hipGetLastError());
     return AC_OK;
 }
@@ -327,7 +339,7 @@ static int estream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int 
     int rc = estream_check(h, B, dec, who);
     if (rc) return rc;
     if (!state_dev) return fail(h, AC_EINVAL, "%s: state is null", who);
-    // a slot that restarted alone would sit in its warm-up hold while the others run: the frame count is one per state, not per slot
+    // (a lockstep stream's frame count is one per state; slots restart alone through ac_encodec_stream_reset_slots)
     if (reset_mask_dev) return fail(h, AC_EINVAL, "%s: EnCodec streams reset together (reset_mask_dev must be NULL)", who);
     const EStreamLayout Ls = estream_layout(h, B, dec);
     if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "%s: state of %zu bytes, %zu needed", who, state_bytes, Ls.total);
@@ -339,18 +351,26 @@ static int estream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int 
                        reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh), static_cast<const uint8_t*>(nullptr), B);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemsetAsync(s + Ls.lstm_h, 0, Ls.lstm_bytes, st));      // h = c = 0; the conv histories are rebuilt from the first push
-    (dec ? h->encodec_dstreams : h->encodec_streams)[state_dev] = ac_handle::EStreamReg{B, true};
+    (dec ? h->encodec_dstreams : h->encodec_streams)[state_dev] = ac_handle::EStreamReg{B, std::vector<uint8_t>((size_t)B, 1)};
     (dec ? h->encodec_streams : h->encodec_dstreams).erase(state_dev);   // (the header just written ends its life as the other kind)
     return AC_OK;
 }
 
-// the checks of a push that touch nothing; *reg: the handle's record of the state
-static int estream_push_check(ac_handle* h, void* state_dev, size_t state_bytes, const void* in, const void* out, int B, int F, int K, bool dec,
-                              const char* who, EStreamLayout* Ls, ac_handle::EStreamReg** reg) {
-    int rc = estream_check(h, B, dec, who);
-    if (rc) return rc;
-    if (!state_dev || !in || !out || F < 1) return fail(h, AC_EINVAL, "%s: bad argument (F=%d)", who, F);
-    if (K < 1 || K > h->cfg.num_quantizers) return fail(h, AC_EINVAL, "%s: K=%d outside [1, %d]", who, K, h->cfg.num_quantizers);
+// a slot list (host memory): 1 <= n <= B entries in [0, B), none twice
+static int estream_slots_check(ac_handle* h, const int* slots, int n, int B, const char* who) {
+    if (n < 1 || n > B) return fail(h, AC_EINVAL, "%s: n=%d slots of a state of %d", who, n, B);
+    std::vector<uint8_t> seen((size_t)B, 0);
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= B) return fail(h, AC_EINVAL, "%s: slot %d outside [0, %d)", who, slots[i], B);
+        if (seen[slots[i]]) return fail(h, AC_EINVAL, "%s: slot %d listed twice", who, slots[i]);
+        seen[slots[i]] = 1;
+    }
+    return AC_OK;
+}
+
+// the handle's record of a state of `B` streams, and its layout, or the refusal
+static int estream_find(ac_handle* h, void* state_dev, size_t state_bytes, int B, bool dec, const char* who, EStreamLayout* Ls,
+                        ac_handle::EStreamReg** reg) {
     auto& mine = dec ? h->encodec_dstreams : h->encodec_streams;
     auto& other = dec ? h->encodec_streams : h->encodec_dstreams;
     auto it = mine.find(state_dev);
@@ -360,11 +380,94 @@ static int estream_push_check(ac_handle* h, void* state_dev, size_t state_bytes,
     if (it->second.B != B) return fail(h, AC_EINVAL, "%s: the state holds %d streams, B=%d", who, it->second.B, B);
     *Ls = estream_layout(h, B, dec);
     if (state_bytes < Ls->total) return fail(h, AC_ENOMEM, "%s: state of %zu bytes, %zu needed", who, state_bytes, Ls->total);
-    if (it->second.fresh && F < warmup_frames(h))
-        return fail(h, AC_EINVAL, "%s: the first push after a reset must bring %d frames (reflect padding of the frame-rate convs), got F=%d", who,
-                    warmup_frames(h), F);
-    if ((rc = check_len(h, (long long)F * h->hop))) return rc;
     *reg = &it->second;
+    return AC_OK;
+}
+
+// The checks of a push that touch nothing; *reg: the handle's record of the state.  `slots` (host; null: a lockstep push of all B
+// streams): the n listed streams -- in range, distinct -- are the ones whose freshness decides the warm-up rule.
+static int estream_push_check(ac_handle* h, void* state_dev, size_t state_bytes, const void* in, const void* out, int B, const int* slots, int n,
+                              int F, int K, bool dec, const char* who, EStreamLayout* Ls, ac_handle::EStreamReg** reg) {
+    int rc = estream_check(h, B, dec, who);
+    if (rc) return rc;
+    if (!state_dev || !in || !out || F < 1) return fail(h, AC_EINVAL, "%s: bad argument (F=%d)", who, F);
+    if (K < 1 || K > h->cfg.num_quantizers) return fail(h, AC_EINVAL, "%s: K=%d outside [1, %d]", who, K, h->cfg.num_quantizers);
+    if ((rc = estream_find(h, state_dev, state_bytes, B, dec, who, Ls, reg))) return rc;
+    const std::vector<uint8_t>& fresh = (*reg)->fresh;
+    bool any_fresh = false;
+    if (slots) {
+        if ((rc = estream_slots_check(h, slots, n, B, who))) return rc;
+        for (int i = 0; i < n; ++i) any_fresh = any_fresh || fresh[slots[i]];
+    } else {
+        for (int b = 0; b < B; ++b) any_fresh = any_fresh || fresh[b];
+    }
+    if (any_fresh && F < warmup_frames(h))
+        return fail(h, AC_EINVAL, "%s: the first push of a stream after its reset must bring %d frames (reflect padding of the frame-rate convs), got F=%d",
+                    who, warmup_frames(h), F);
+    return check_len(h, (long long)F * h->hop);
+}
+
+// ac_encodec_stream_reset_slots / _decode_reset_slots: the listed streams start afresh, the others and the header stay as they are
+static int estream_reset_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n, void* stream,
+                               bool dec) {
+    const char* who = dec ? "ac_encodec_stream_decode_reset_slots" : "ac_encodec_stream_reset_slots";
+    int rc = estream_check(h, B, dec, who);
+    if (rc) return rc;
+    if (!state_dev || !slots_host || !slots_dev) return fail(h, AC_EINVAL, "%s: null argument", who);
+    EStreamLayout Ls;
+    ac_handle::EStreamReg* reg = nullptr;
+    if ((rc = estream_find(h, state_dev, state_bytes, B, dec, who, &Ls, &reg))) return rc;
+    if ((rc = estream_slots_check(h, slots_host, n, B, who))) return rc;
+    const LstmPlan& lp = dec ? h->dec_lstm : h->enc_lstm;
+    char* s = static_cast<char*>(state_dev);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(estream_reset_slots_kernel<>, dim3(n), dim3(256), 0, st, reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh),
+                       reinterpret_cast<float*>(s + Ls.lstm_h), reinterpret_cast<float*>(s + Ls.lstm_c), slots_dev, n, B, std::max(lp.layers, 1), h->D);
+    HIPCHK(h, hipGetLastError());
+    for (int i = 0; i < n; ++i) reg->fresh[slots_host[i]] = 1;
+    return AC_OK;
+}
+
+// One push of n streams of a state of B: all of them in order (a lockstep push: slots_host = slots_dev = null, n = B) or the listed
+// ones.  Every buffer and launch shape is that of a dense push of n streams; `slots_dev` only redirects the addresses into the state.
+static int estream_encode(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                          const float* sig_dev, int F, int K, int64_t* toks_dev, void* ws, size_t ws_bytes, void* stream, const char* who) {
+    EStreamLayout Ls;
+    ac_handle::EStreamReg* reg = nullptr;
+    int rc = estream_push_check(h, state_dev, state_bytes, sig_dev, toks_dev, B, slots_host, n, F, K, false, who, &Ls, &reg);
+    if (rc) return rc;
+    const Workspace w = estream_plan_ws(h, n, F, false);
+    WsPtrs p;
+    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = amax_begin(h, st, n))) return rc;
+    float* feats = p.lstm.gin;        // free again once the LSTM is done (as ac_encode)
+    rc = estream_encoder(h, st, static_cast<char*>(state_dev), Ls, slots_dev, sig_dev, n, F, feats, p, w.act_floats);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) reg->fresh[slots_host ? slots_host[i] : i] = 0;
+    return rvq_encode_fwd(h, st, feats, n * F, K, reinterpret_cast<long long*>(toks_dev));
+}
+
+static int estream_decode(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                          const int64_t* toks_dev, int F, int K, float* sig_dev, void* ws, size_t ws_bytes, void* stream, const char* who) {
+    EStreamLayout Ls;
+    ac_handle::EStreamReg* reg = nullptr;
+    int rc = estream_push_check(h, state_dev, state_bytes, toks_dev, sig_dev, B, slots_host, n, F, K, true, who, &Ls, &reg);
+    if (rc) return rc;
+    const Workspace w = estream_plan_ws(h, n, F, true);
+    WsPtrs p;
+    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = amax_begin(h, st, n))) return rc;
+    rc = estream_decoder(h, st, static_cast<char*>(state_dev), Ls, slots_dev, reinterpret_cast<const long long*>(toks_dev), n, F, K, sig_dev, p, w.act_floats);
+    if (!rc)
+        for (int i = 0; i < n; ++i) reg->fresh[slots_host ? slots_host[i] : i] = 0;
+    return rc;
+}
+
+// a slot call's own arguments (the rest is the push's); a null handle falls through to the push's check
+static int eslots_args(ac_handle* h, const int* slots_host, const int* slots_dev, const char* who) {
+    if (h && (!slots_host || !slots_dev)) return fail(h, AC_EINVAL, "%s: the slot list is null", who);
     return AC_OK;
 }
 
@@ -390,20 +493,7 @@ int ac_encodec_stream_reset(ac_handle* h, void* state_dev, size_t state_bytes, i
 
 int ac_encodec_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, const float* sig_dev, int B, int F, int K, int64_t* toks_dev,
                              void* ws, size_t ws_bytes, void* stream) {
-    EStreamLayout Ls;
-    ac_handle::EStreamReg* reg = nullptr;
-    int rc = estream_push_check(h, state_dev, state_bytes, sig_dev, toks_dev, B, F, K, false, "ac_encodec_stream_encode", &Ls, &reg);
-    if (rc) return rc;
-    const Workspace w = estream_plan_ws(h, B, F, false);
-    WsPtrs p;
-    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = amax_begin(h, st, B))) return rc;
-    float* feats = p.lstm.gin;        // free again once the LSTM is done (as ac_encode)
-    rc = estream_encoder(h, st, static_cast<char*>(state_dev), Ls, sig_dev, B, F, feats, p, w.act_floats);
-    if (rc) return rc;
-    reg->fresh = false;
-    return rvq_encode_fwd(h, st, feats, B * F, K, reinterpret_cast<long long*>(toks_dev));
+    return estream_encode(h, state_dev, state_bytes, B, nullptr, nullptr, B, sig_dev, F, K, toks_dev, ws, ws_bytes, stream, "ac_encodec_stream_encode");
 }
 
 size_t ac_encodec_stream_decode_state_bytes(const ac_handle* h, int B) {
@@ -422,18 +512,31 @@ int ac_encodec_stream_decode_reset(ac_handle* h, void* state_dev, size_t state_b
 
 int ac_encodec_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K, float* sig_dev,
                              void* ws, size_t ws_bytes, void* stream) {
-    EStreamLayout Ls;
-    ac_handle::EStreamReg* reg = nullptr;
-    int rc = estream_push_check(h, state_dev, state_bytes, toks_dev, sig_dev, B, F, K, true, "ac_encodec_stream_decode", &Ls, &reg);
-    if (rc) return rc;
-    const Workspace w = estream_plan_ws(h, B, F, true);
-    WsPtrs p;
-    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = amax_begin(h, st, B))) return rc;
-    rc = estream_decoder(h, st, static_cast<char*>(state_dev), Ls, reinterpret_cast<const long long*>(toks_dev), B, F, K, sig_dev, p, w.act_floats);
-    if (!rc) reg->fresh = false;
-    return rc;
+    return estream_decode(h, state_dev, state_bytes, B, nullptr, nullptr, B, toks_dev, F, K, sig_dev, ws, ws_bytes, stream, "ac_encodec_stream_decode");
+}
+
+int ac_encodec_stream_reset_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                                  void* stream) {
+    return estream_reset_slots(h, state_dev, state_bytes, B, slots_host, slots_dev, n, stream, false);
+}
+
+int ac_encodec_stream_decode_reset_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                                         void* stream) {
+    return estream_reset_slots(h, state_dev, state_bytes, B, slots_host, slots_dev, n, stream, true);
+}
+
+int ac_encodec_stream_encode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                                   const float* sig_dev, int F, int K, int64_t* toks_dev, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "ac_encodec_stream_encode_slots";
+    const int rc = eslots_args(h, slots_host, slots_dev, who);
+    return rc ? rc : estream_encode(h, state_dev, state_bytes, B, slots_host, slots_dev, n, sig_dev, F, K, toks_dev, ws, ws_bytes, stream, who);
+}
+
+int ac_encodec_stream_decode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                                   const int64_t* toks_dev, int F, int K, float* sig_dev, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "ac_encodec_stream_decode_slots";
+    const int rc = eslots_args(h, slots_host, slots_dev, who);
+    return rc ? rc : estream_decode(h, state_dev, state_bytes, B, slots_host, slots_dev, n, toks_dev, F, K, sig_dev, ws, ws_bytes, stream, who);
 }
 
 }  // extern "C"

@@ -281,7 +281,7 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
         return rc;
     ws.give(stg);
     hipLaunchKernelGGL(mstream_advance_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
-                       reinterpret_cast<int*>(state + Ls.fresh), B, T25);
+                       reinterpret_cast<int*>(state + Ls.fresh), B, T25, static_cast<const int*>(nullptr), B);   // (no slot map: stream_stage.h)
     HIPCHK(h, hipGetLastError());
     return AC_OK;
 }
@@ -362,7 +362,7 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
     if ((rc = mstream_conv(h, st, m.dec_head, staged_act(stg, B, Ts + Ls.conv_P[l], Fh), c.last_kernel_size, 1, Ts, Out{sig, nullptr}, B, nullptr))) return rc;
     ws.give(stg);
     hipLaunchKernelGGL(mstream_advance_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
-                       reinterpret_cast<int*>(state + Ls.fresh), B, T25);
+                       reinterpret_cast<int*>(state + Ls.fresh), B, T25, static_cast<const int*>(nullptr), B);   // (no slot map: stream_stage.h)
     HIPCHK(h, hipGetLastError());
     return AC_OK;
 }

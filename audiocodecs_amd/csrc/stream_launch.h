@@ -10,10 +10,11 @@ static unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n 
 static Act staged_act(const float* p, int B, int rows, int C) { return Act{p, (long long)rows * C, C, rows, C}; }
 
 // [cache | x] -> staged (a fresh activation buffer of B * (P + L) * C floats); x's last P rows -> cache.  `cache` [B][P][C] and
-// `fresh` [B] live in the stream state; `mode` (STAGE_*) is a fresh stream's history.
+// `fresh` [B] live in the stream state; `mode` (STAGE_*) is a fresh stream's history.  `slot` (device, [B]; null = identity): the push's
+// row b addresses stream slot[b] of the `slot_cap` streams the state holds; x and staged stay dense.
 // (`any_L`: a chunk shorter than the history is staged in two launches -- stream_stage.h mstream_stage_ro_kernel)
 static int stream_stage(ac_handle* h, hipStream_t st, float* cache, const int* fresh, int P, int C, int l, const Act& x, int B, float* staged,
-                        size_t cap, int mode, bool any_L) {
+                        size_t cap, int mode, bool any_L, const int* slot = nullptr, int slot_cap = 0) {
     MStreamStageParams p{};
     p.P = P;
     p.C = C;
@@ -29,6 +30,8 @@ static int stream_stage(ac_handle* h, hipStream_t st, float* cache, const int* f
     p.B = B;
     p.L = x.L;
     p.replicate = mode;
+    p.slot = slot;
+    p.cap = slot ? slot_cap : B;
     const long long n = (long long)B * (p.P + x.L) * p.C;
     if (x.L < p.P) {
         {

@@ -5,6 +5,9 @@
 //   mstream_linear_kernel  Y[R][N] = epilogue(X[R][K] W^T) for the few rows of a push: weights streamed, exact fp32 FMAs
 //   mstream_advance_kernel position += rows, fresh = 0 (the last launch of a push)
 //   mstream_reset_kernel   header + (masked) position = 0, fresh = 1
+// A push may serve a SUBSET of the state's streams: its activations are dense ([n] rows), and only the addresses into the stream state
+// (cache, fresh, position) go through a slot map -- `slot` [n], row b of the push belongs to stream slot[b]; null = identity
+// (mstream_slot).  Mimi passes null everywhere; EnCodec's slot pushes pass the caller's list (encodec_stream.hip).
 // Every kernel here is a template (the dummy parameter of those that need none): two translation units include this header, and the
 // library keeps one definition of every non-template kernel (core.h).
 #pragma once
@@ -31,7 +34,17 @@ struct MStreamStageParams {
     const int* fresh;            // [B]
     int B, P, L, C;
     int replicate;               // a fresh stream's history: STAGE_*
+    const int* slot;             // null: row b is stream b.  Else [B] (device): row b is stream slot[b] of the `cap` the state holds
+    int cap;
 };
+
+// The stream of the state that row b of a push addresses, or -1 when the map's entry is outside [0, cap): such a row neither reads nor
+// writes the state, whatever the device copy of the list holds.
+__device__ __forceinline__ int mstream_slot(const int* slot, int b, int cap) {
+    if (!slot) return b;
+    const int s = slot[b];
+    return (unsigned)s < (unsigned)cap ? s : -1;
+}
 
 // history row r (0 .. P-1, position r - P) of a fresh stream
 __device__ __forceinline__ float mstream_fresh_row(const MStreamStageParams& p, const float* xb, int r, int c) {
@@ -51,9 +64,13 @@ __global__ __launch_bounds__(256) void mstream_stage_kernel(const MStreamStagePa
         const float* xb = p.x + (long long)b * p.bs;
         float v;
         if (r < p.P) {
-            float* cr = p.cache + ((long long)b * p.P + r) * p.C + c;
-            v = p.fresh[b] ? mstream_fresh_row(p, xb, r, c) : *cr;
-            *cr = xb[(long long)(p.L - p.P + r) * p.ts + c];
+            const int sb = mstream_slot(p.slot, b, p.cap);
+            v = 0.f;
+            if (sb >= 0) {
+                float* cr = p.cache + ((long long)sb * p.P + r) * p.C + c;
+                v = p.fresh[sb] ? mstream_fresh_row(p, xb, r, c) : *cr;
+                *cr = xb[(long long)(p.L - p.P + r) * p.ts + c];
+            }
         } else {
             v = xb[(long long)(r - p.P) * p.ts + c];
         }
@@ -74,8 +91,13 @@ __global__ __launch_bounds__(256) void mstream_stage_ro_kernel(const MStreamStag
         const int r = (int)(br % rows), b = (int)(br / rows);
         const float* xb = p.x + (long long)b * p.bs;
         float v;
-        if (r < p.P) v = p.fresh[b] ? mstream_fresh_row(p, xb, r, c) : p.cache[((long long)b * p.P + r) * p.C + c];
-        else v = xb[(long long)(r - p.P) * p.ts + c];
+        if (r < p.P) {
+            const int sb = mstream_slot(p.slot, b, p.cap);
+            v = 0.f;
+            if (sb >= 0) v = p.fresh[sb] ? mstream_fresh_row(p, xb, r, c) : p.cache[((long long)sb * p.P + r) * p.C + c];
+        } else {
+            v = xb[(long long)(r - p.P) * p.ts + c];
+        }
         p.y[e] = v;
     }
 }
@@ -88,7 +110,8 @@ __global__ __launch_bounds__(256) void mstream_cache_tail_kernel(const MStreamSt
         const int c = (int)(e % p.C);
         const long long br = e / p.C;
         const int r = (int)(br % p.P), b = (int)(br / p.P);
-        p.cache[e] = p.y[((long long)b * (p.P + p.L) + p.L + r) * p.C + c];
+        const int sb = mstream_slot(p.slot, b, p.cap);
+        if (sb >= 0) p.cache[((long long)sb * p.P + r) * p.C + c] = p.y[((long long)b * (p.P + p.L) + p.L + r) * p.C + c];
     }
 }
 
@@ -171,11 +194,14 @@ __global__ __launch_bounds__(64 * KS) void mstream_linear_kernel(const MStreamLi
 }
 
 template <int U = 0>
-__global__ __launch_bounds__(64) void mstream_advance_kernel(long long* pos, int* fresh, int B, int rows) {
+__global__ __launch_bounds__(64) void mstream_advance_kernel(long long* pos, int* fresh, int B, int rows, const int* slot, int cap) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b < B) {
-        pos[b] += rows;
-        fresh[b] = 0;
+        const int sb = mstream_slot(slot, b, cap);
+        if (sb >= 0) {
+            pos[sb] += rows;
+            fresh[sb] = 0;
+        }
     }
 }
 

@@ -17,8 +17,9 @@ from . import _native, checkpoint
 from .codec import Codec
 from .config import ENCODEC_24KHZ, EncodecConfig
 from .resample import ResampleStream
+from .sessions import plan_push
 
-__all__ = ["Encodec", "EncodecEncodeStream", "EncodecDecodeStream"]
+__all__ = ["Encodec", "EncodecEncodeStream", "EncodecDecodeStream", "EncodecEncodeSessions", "EncodecDecodeSessions"]
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -267,16 +268,17 @@ class Encodec(Codec):
 
     # ---- streaming -------------------------------------------------------------------------------
     def _stream_checks(self, what: str, batch_size, device, resample=False) -> _Native:
-        need, lacks = ("encoder", "decode") if what == "encode_stream" else ("decoder", "encode")
+        need, lacks = ("encoder", "decode") if what.startswith("encode") else ("decoder", "encode")
+        pool = what.endswith("sessions")
         if self.mode == lacks:
             raise ValueError(f"{what} needs the {need}: this Encodec was built with mode=\"{lacks}\"")
         if self.sample_rate != self.config.sampling_rate and not resample:
             raise ValueError(
                 f"{what} runs at the codec's own rate ({self.config.sampling_rate} Hz): streaming resampling from or to "
-                f"sample_rate={self.sample_rate} is opt-in, pass resample=True"
+                f"sample_rate={self.sample_rate} is " + ("not available per slot" if pool else "opt-in, pass resample=True")
             )
         if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
-            raise ValueError(f"`batch_size` ({batch_size!r}) must be a positive int")
+            raise ValueError(f"`{'capacity' if pool else 'batch_size'}` ({batch_size!r}) must be a positive int")
         self._num_quantizers()
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         return self._native_for(torch.empty(0, device=dev))
@@ -294,6 +296,16 @@ class Encodec(Codec):
         frames it was given (include/audiocodecs_amd.h ac_encodec_stream_decode*).  `resample=True`:
         the samples come out at `sample_rate`, through a `ResampleStream` behind the decoder (`finish` returns its tail)."""
         return EncodecDecodeStream(self, self._stream_checks("decode_stream", batch_size, device, resample), batch_size, bool(resample))
+
+    def encode_sessions(self, capacity: int, device=None) -> "EncodecEncodeSessions":
+        """A pool of up to `capacity` independent encode sessions on one stream state: sessions `open` and `close` at any time and
+        `push(slots, sig)` serves any subset of them, each with the warm-up hold and the bits of a lone `encode_stream(1)`
+        (DESIGN.md section 8f).  Runs at the codec's own rate only."""
+        return EncodecEncodeSessions(self, self._stream_checks("encode_sessions", capacity, device), capacity)
+
+    def decode_sessions(self, capacity: int, device=None) -> "EncodecDecodeSessions":
+        """The decode side of `encode_sessions`: `push(slots, toks)` returns every listed session's samples."""
+        return EncodecDecodeSessions(self, self._stream_checks("decode_sessions", capacity, device), capacity)
 
     # ---- measurement hook used by bench.py ------------------------------------------------------
     def profile_kernels(self, fn):
@@ -518,3 +530,192 @@ class EncodecDecodeStream(_EncodecStream):
         self._run(chunk, n, sig)
         self._held = self._held[:, :0]
         return sig
+
+
+class _EncodecSessions:
+    """A pool of independent sessions on one EnCodec stream state (include/audiocodecs_amd.h ac_encodec_stream_*_slots).
+
+    The state holds `capacity` slots.  `open` hands out the lowest free one and restarts it alone; `push(slots, x)` runs any subset,
+    row i of `x` belonging to `slots[i]`.  A slot follows the rule a whole lockstep stream follows (`_EncodecStream`): partial frames
+    wait, a fresh slot holds until `WARMUP_FRAMES` whole frames are in and releases them in one go.  The rows of a push that run the
+    same number of frames share one native call, the groups going out in ascending F (sessions.plan_push); a slot's bits are those of
+    a lone stream fed the same pieces, whichever slot it sits in and whatever the others do."""
+
+    _unit = 1          # units per frame in what a slot holds back: samples on the encode side, token frames on the decode side
+
+    def __init__(self, codec: Encodec, nat: _Native, capacity: int, kind: str):
+        self.codec = codec
+        self._nat = nat
+        self.capacity = capacity
+        self.num_codebooks = codec._num_quantizers()
+        self.hop = codec.config.hop_length
+        self.WARMUP_FRAMES = max(codec.config.kernel_size, codec.config.last_kernel_size)
+        self.device = nat.device
+        L = nat.lib
+        self._fns = {
+            "encode": (L.ac_encodec_stream_state_bytes, L.ac_encodec_stream_reset, L.ac_encodec_stream_workspace_bytes,
+                       L.ac_encodec_stream_encode_slots, L.ac_encodec_stream_reset_slots),
+            "decode": (L.ac_encodec_stream_decode_state_bytes, L.ac_encodec_stream_decode_reset, L.ac_encodec_stream_decode_workspace_bytes,
+                       L.ac_encodec_stream_decode_slots, L.ac_encodec_stream_decode_reset_slots),
+        }[kind]
+        self._kind = kind
+        nbytes = self._fns[0](nat.h, capacity)
+        if nbytes == 0:
+            raise _native.NativeError(f"ac_encodec_stream_{'decode_' if kind == 'decode' else ''}state_bytes returned 0")
+        self._state_buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self._state_buf.data_ptr()) % 256
+        self._state = self._state_buf[off:off + nbytes]
+        self._ws = None
+        self._is_open = [False] * capacity
+        self._ran = [0] * capacity              # frames run since the slot was opened
+        self._held = [self._empty()] * capacity  # what waits per slot: [m] samples / [m, K] tokens
+        with torch.cuda.device(self.device):    # the one whole reset: the header, and the handle's record of the address
+            _native.check(self._fns[1](nat.h, _ptr(self._state), self._state.numel(), capacity, None, _stream()), nat.h,
+                          f"ac_encodec_stream_{kind}_reset")
+
+    # -- the slots -----------------------------------------------------------------------------------------------------------------
+    @property
+    def active(self):
+        """The open slots, ascending."""
+        return [s for s in range(self.capacity) if self._is_open[s]]
+
+    def _slot(self, slot) -> int:
+        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.capacity:
+            raise ValueError(f"slot {slot!r} is outside [0, {self.capacity})")
+        if not self._is_open[slot]:
+            raise ValueError(f"slot {slot} is not open")
+        return slot
+
+    def pending(self, slot: int) -> int:
+        """Units of `slot` that have not run: samples on the encode side, token frames on the decode side."""
+        return int(self._held[self._slot(slot)].shape[0])
+
+    def frames(self, slot: int) -> int:
+        """Frames `slot` has run since it was opened."""
+        return self._ran[self._slot(slot)]
+
+    def _slot_lists(self, slots):
+        host = (C.c_int * len(slots))(*slots)
+        return host, torch.tensor(list(slots), dtype=torch.int32, device=self.device)
+
+    @torch.no_grad()
+    def open(self) -> int:
+        """Take the lowest free slot and restart it alone (the others keep running); ValueError when the pool is full."""
+        free = [s for s in range(self.capacity) if not self._is_open[s]]
+        if not free:
+            raise ValueError(f"the pool is full: all {self.capacity} slots are open")
+        slot = free[0]
+        nat = self._nat
+        with torch.cuda.device(self.device):
+            host, dev = self._slot_lists([slot])
+            _native.check(self._fns[4](nat.h, _ptr(self._state), self._state.numel(), self.capacity, host, _ptr(dev), 1, _stream()), nat.h,
+                          f"ac_encodec_stream_{self._kind}_reset_slots")
+        self._is_open[slot] = True
+        self._ran[slot] = 0
+        self._held[slot] = self._empty()
+        return slot
+
+    def close(self, slot: int) -> None:
+        """Free `slot`, dropping what it holds (held warm-up frames included)."""
+        slot = self._slot(slot)
+        self._is_open[slot] = False
+        self._held[slot] = self._empty()
+
+    # -- a push --------------------------------------------------------------------------------------------------------------------
+    def _check_push(self, slots, x):
+        try:
+            slots = list(slots)
+        except TypeError:
+            raise ValueError(f"push expects a sequence of slots, got {type(slots)}")
+        for s in slots:
+            self._slot(s)
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"push: a slot is listed twice in {slots}")
+        self._check_rows(len(slots), x)
+        return slots
+
+    def _run(self, slots, src: torch.Tensor, F: int, dst: torch.Tensor) -> None:
+        nat, n = self._nat, len(slots)
+        with torch.cuda.device(self.device):
+            need = self._fns[2](nat.h, n, F)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            host, dev = self._slot_lists(slots)
+            _native.check(self._fns[3](nat.h, _ptr(self._state), self._state.numel(), self.capacity, host, _ptr(dev), n, _ptr(src), F,
+                                       self.num_codebooks, _ptr(dst), _ptr(self._ws), self._ws.numel(), _stream()), nat.h,
+                          f"ac_encodec_stream_{self._kind}_slots")
+        for s in slots:
+            self._ran[s] += F
+
+    @torch.no_grad()
+    def push(self, slots, x: torch.Tensor):
+        """Feed row i of `x` to `slots[i]` (n distinct open slots); returns n tensors, what each slot releases (possibly nothing)."""
+        slots = self._check_push(slots, x)
+        unit = self._unit
+        whole = [torch.cat([self._held[s], x[i]], 0) if self._held[s].shape[0] else x[i] for i, s in enumerate(slots)]
+        plan = plan_push([int(self._held[s].shape[0]) for s in slots], [self._ran[s] for s in slots], [int(x.shape[1])] * len(slots),
+                         unit, self.WARMUP_FRAMES)
+        out = [self._nothing() for _ in slots]
+        for F, rows in plan:
+            src = torch.stack([whole[i][: F * unit] for i in rows], 0).contiguous()
+            dst = self._result(len(rows), F)
+            self._run([slots[i] for i in rows], src, F, dst)
+            for j, i in enumerate(rows):
+                out[i] = dst[j]
+                whole[i] = whole[i][F * unit:]
+        for i, s in enumerate(slots):
+            self._held[s] = whole[i].clone()
+        return out
+
+
+class EncodecEncodeSessions(_EncodecSessions):
+    """A pool of encode sessions (Encodec.encode_sessions).  `push(slots, sig)`: `sig` is [n, L] fp32 on the codec's device, any
+    L >= 0; returns n int64 tensors [f_i, K], the tokens of the frames each slot releases."""
+
+    def __init__(self, codec: Encodec, nat: _Native, capacity: int):
+        self._unit = codec.config.hop_length
+        super().__init__(codec, nat, capacity, "encode")
+
+    def _empty(self):
+        return torch.empty(0, dtype=torch.float32, device=self.device)
+
+    def _nothing(self):
+        return torch.empty(0, self.num_codebooks, dtype=torch.int64, device=self.device)
+
+    def _result(self, n, F):
+        return torch.empty(n, F, self.num_codebooks, dtype=torch.int64, device=self.device)
+
+    def _check_rows(self, n, sig):
+        if not isinstance(sig, torch.Tensor) or sig.dim() != 2 or sig.shape[0] != n:
+            raise ValueError(f"push expects a [{n}, L] tensor for {n} slots, got {tuple(sig.shape) if isinstance(sig, torch.Tensor) else type(sig)}")
+        if sig.dtype != torch.float32:
+            raise ValueError(f"push expects float32 samples, got {sig.dtype}")
+        if sig.device != self.device:
+            raise ValueError(f"push expects samples on {self.device}, got {sig.device}")
+
+
+class EncodecDecodeSessions(_EncodecSessions):
+    """A pool of decode sessions (Encodec.decode_sessions).  `push(slots, toks)`: `toks` is [n, F, K] int64 on the codec's device,
+    K = the codec's stage count, any F >= 0; returns n fp32 tensors [f_i * hop], the samples of the frames each slot releases."""
+
+    def __init__(self, codec: Encodec, nat: _Native, capacity: int):
+        super().__init__(codec, nat, capacity, "decode")
+
+    def _empty(self):
+        return torch.empty(0, self.num_codebooks, dtype=torch.int64, device=self.device)
+
+    def _nothing(self):
+        return torch.empty(0, dtype=torch.float32, device=self.device)
+
+    def _result(self, n, F):
+        return torch.empty(n, F * self.hop, dtype=torch.float32, device=self.device)
+
+    def _check_rows(self, n, toks):
+        K = self.num_codebooks
+        if not isinstance(toks, torch.Tensor) or toks.dim() != 3 or toks.shape[0] != n or toks.shape[2] != K:
+            raise ValueError(f"push expects a [{n}, F, {K}] tensor for {n} slots, got {tuple(toks.shape) if isinstance(toks, torch.Tensor) else type(toks)}")
+        if toks.dtype != torch.int64:
+            raise ValueError(f"push expects int64 tokens, got {toks.dtype}")
+        if toks.device != self.device:
+            raise ValueError(f"push expects tokens on {self.device}, got {toks.device}")

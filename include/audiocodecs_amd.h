@@ -351,6 +351,37 @@ size_t ac_encodec_stream_decode_workspace_bytes(const ac_handle* h, int B, int F
 int ac_encodec_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K,
                              float* sig_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Independent sessions on one EnCodec stream state: pushes and resets of a SUBSET of its B streams ("slots").
+ * A state is prepared once, whole, by ac_encodec_stream_reset / _decode_reset (that call writes the header and registers the address);
+ * from then on the calls below restart and run any of its slots while the others keep what they hold.
+ *   slots_host [n]  the slot list in host memory: 1 <= n <= B distinct values in [0, B).  The library reads it for every check, all
+ *                   decided before anything is launched.
+ *   slots_dev  [n]  the caller's device copy of the same list, which the kernels read (the library neither allocates nor copies).
+ *                   Whatever it holds, the kernels index only inside the state: an entry outside [0, B) makes that row touch no state.
+ * ac_encodec_stream_reset_slots / _decode_reset_slots: the listed slots start afresh (frame count 0, fresh, LSTM h = c = 0) in one
+ * launch; no other byte of the state changes.
+ * ac_encodec_stream_encode_slots / _decode_slots: one push of F whole frames for the n listed slots.  Row i of sig_dev [n, F * hop] /
+ * toks_dev [n, F, K] belongs to slot slots_host[i]; every buffer, scale and launch is that of a lockstep push of B = n streams, so the
+ * workspace is ac_encodec_stream_workspace_bytes(h, n, F) / _decode_workspace_bytes(h, n, F), and the bits of a slot's result are those
+ * of the lockstep stream fed the same rows: they depend neither on the slot's index, nor on the order of the list, nor on what the other
+ * rows or the unlisted slots carry.  The handle keeps a freshness flag per slot: if ANY listed slot is fresh (no push since its reset),
+ * F >= max(kernel_size, last_kernel_size) (7), AC_EINVAL otherwise; fresh and warm slots may share a call when F allows.  A lockstep
+ * push (ac_encodec_stream_encode / _decode) on the same state is the push of all B slots in order, and needs the warm-up F while any
+ * slot is fresh.
+ * AC_EINVAL for a state never reset whole on this handle, reset as the other kind or for another B, n outside [1, B], a slot outside
+ * [0, B) or listed twice, a null pointer, K out of range, a non-EnCodec handle; AC_ENOMEM for a short state or workspace; AC_ESTATE
+ * for a handle loaded without the half it needs.  After a refusal the handle and the state are as they were. */
+int ac_encodec_stream_reset_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev,
+                                  int n, void* stream);
+int ac_encodec_stream_decode_reset_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host,
+                                         const int* slots_dev, int n, void* stream);
+int ac_encodec_stream_encode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev,
+                                   int n, const float* sig_dev, int F, int K, int64_t* toks_dev, void* workspace_dev,
+                                   size_t workspace_bytes, void* stream);
+int ac_encodec_stream_decode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev,
+                                   int n, const int64_t* toks_dev, int F, int K, float* sig_dev, void* workspace_dev,
+                                   size_t workspace_bytes, void* stream);
+
 /* Copy the first K codebooks to embs_dev [K, codebook_size, ac_codebook_dim] fp32 (encodec.py:74-79;
  * mimi.py:52-62 `latent=True`). */
 int ac_embs(ac_handle* h, int K, float* embs_dev, void* stream);

@@ -5,6 +5,7 @@ seeded synthetic weights, noise input / random tokens.
     python tools/encodec_stream_latency.py --batch 1 --frames 1 [--pushes 200 --warmup 20] [--direction decode]
     python tools/encodec_stream_latency.py --sweep [--out profiles/encodec_stream_latency.json]
     python tools/encodec_stream_latency.py --sweep --sample-rate 16000 --out profiles/encodec_stream_latency_16k.json
+    python tools/encodec_stream_latency.py --sessions --out profiles/encodec_sessions_latency.json
 
 Same method as tools/mimi_stream_latency.py: after the stream's own start-up hold (one push of WARMUP_FRAMES frames, not timed) and
 `--warmup` untimed pushes, every push is timed on the host from `push` to a stream synchronisation (what a caller waiting for its
@@ -18,7 +19,14 @@ in both directions; `--out` also writes the lines as one JSON list.
 24 kHz stream ("resample": false) and as `encode_stream / decode_stream(B, resample=True)` of a codec built for rate R ("resample":
 true), whose pushes carry the same audio time (F frames; at 16 kHz an encode push is 213 or 214 samples per frame) and pass the
 stateful resampler (ResampleStream: two launches per push, not on a handle, so not in the per-kernel split).  The difference of the
-two medians is the resampler's cost per push."""
+two medians is the resampler's cost per push.
+
+`--sessions` measures session pools (Encodec.encode_sessions / decode_sessions): a pool of capacity 64 with
+n = 1 / 8 / 64 listed slots against the lockstep stream of batch n, one-frame pushes in both directions.  The two run in one process
+on ALTERNATING pushes (pool, stream, pool, ...), so that clock and cache state are shared; after each one's start-up release and
+`--warmup` untimed pushes, `--pushes` pushes of each are timed as above.  "mixed tick" is the pool's push in which one listed slot
+releases its 7 held frames beside n - 1 steady slots (two native calls; the slot is closed, reopened and fed 6 frames, untimed, before
+every timed push).  Nothing is gated on these numbers: the lockstep stream at the same n is the baseline of a subset push."""
 import argparse
 import json
 import os
@@ -95,6 +103,58 @@ def measure(codec, direction, B, F, pushes, warmup, resample=False):
             "kernels_one_push": [{"name": nm, "launches": n, "ms": round(ms, 4)} for nm, n, ms, _, _ in sorted(stats, key=lambda r: -r[2])]}
 
 
+def measure_sessions(codec, direction, n, pushes, warmup, capacity=64):
+    cfg = codec.config
+    hop, K = cfg.hop_length, codec.num_codebooks
+    enc = direction == "encode"
+    pool = codec.encode_sessions(capacity) if enc else codec.decode_sessions(capacity)
+    s = codec.encode_stream(n) if enc else codec.decode_stream(n)
+    W = pool.WARMUP_FRAMES
+    slots = [pool.open() for _ in range(capacity)][:: capacity // n][:n]     # n of the 64 open slots, spread over the state
+    frames = W + warmup + pushes
+    if enc:
+        data = torch.from_numpy((prng.normal(13, "sessions_latency", (n, frames * hop)) * 0.1).astype(np.float32)).cuda()
+        piece = lambda a, m: data[:, a * hop:(a + m) * hop]      # noqa: E731
+    else:
+        data = torch.from_numpy(prng.randint(13, "sessions_latency", (n, frames, K), cfg.codebook_size)).to(torch.int64).cuda()
+        piece = lambda a, m: data[:, a:a + m]                    # noqa: E731
+    unit = hop if enc else 1
+    first = pool.push(slots, piece(0, W))
+    assert all(r.shape[0] == (W if enc else W * hop) for r in first) and s.push(piece(0, W)).shape[1] == first[0].shape[0]
+    torch.cuda.synchronize()
+    lat = {"pool": [], "stream": []}
+    for i in range(warmup + pushes):
+        x = piece(W + i, 1)
+        for who, fn in (("pool", lambda: pool.push(slots, x)), ("stream", lambda: s.push(x))):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i >= warmup:
+                lat[who].append((time.perf_counter() - t0) * 1e3)
+    # the mixed tick: slots[0] is a new session that releases its hold beside the others' one frame
+    mixed = []
+    for i in range(warmup + pushes):
+        pool.close(slots[0])
+        assert pool.open() == slots[0]
+        held = pool.push(slots[:1], piece(0, W - 1)[:1])
+        assert held[0].shape[0] == 0 and pool.pending(slots[0]) == (W - 1) * unit
+        x = piece(W + i, 1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = pool.push(slots, x)
+        torch.cuda.synchronize()
+        if i >= warmup:
+            mixed.append((time.perf_counter() - t0) * 1e3)
+    assert out[0].shape[0] == (W if enc else W * hop) and all(r.shape[0] == (1 if enc else hop) for r in out[1:])
+    stats = codec.profile_kernels(lambda: pool.push(slots, piece(W, 1)))
+    q = lambda v: (round(float(np.median(v)), 3), round(float(np.percentile(v, 99)), 3))      # noqa: E731
+    (pm, pp), (sm, sp), (mm, mp) = q(lat["pool"]), q(lat["stream"]), q(mixed)
+    return {"direction": direction, "capacity": capacity, "listed": n, "frames_per_push": 1, "pushes": pushes, "warmup": warmup,
+            "pool_median_ms": pm, "pool_p99_ms": pp, "stream_median_ms": sm, "stream_p99_ms": sp, "pool_minus_stream_median_ms": round(pm - sm, 3),
+            "mixed_tick_median_ms": mm, "mixed_tick_p99_ms": mp,
+            "launches_one_pool_push": int(sum(k for _, k, _, _, _ in stats)), "kernel_ms_one_pool_push": round(sum(ms for _, _, ms, _, _ in stats), 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1)
@@ -104,6 +164,7 @@ def main():
     ap.add_argument("--precision", default=None, choices=[None, "fp32", "fp32_exact"])
     ap.add_argument("--direction", default="encode", choices=["encode", "decode"])
     ap.add_argument("--sweep", action="store_true", help="B = 1 / 8 / 64 x 1 / 25 frames per push x both directions")
+    ap.add_argument("--sessions", action="store_true", help="session pools of capacity 64, n = 1 / 8 / 64 listed slots, against the lockstep stream of batch n")
     ap.add_argument("--out", default=None, help="also write the result lines to this file as one JSON list")
     ap.add_argument("--sample-rate", type=int, default=24000, help="the caller's rate; another one than 24000 also runs every configuration with resample=True")
     a = ap.parse_args()
@@ -115,6 +176,13 @@ def main():
     if a.sample_rate != cfg.sampling_rate:
         variants.append((Encodec(a.sample_rate, num_codebooks=8, state_dict=sd, config=cfg, precision=a.precision).eval(), True))
     rows = []
+    if a.sessions:
+        runs = []
+        for d in ("encode", "decode"):
+            for n in (1, 8, 64):
+                rows.append(measure_sessions(codec, d, n, a.pushes, a.warmup))
+                rows[-1]["precision"] = a.precision or "default"
+                print(json.dumps(rows[-1]), flush=True)
     for d, B, F in runs:
         for c, rs in variants:
             rows.append(measure(c, d, B, F, a.pushes, a.warmup, rs))
