@@ -30,6 +30,8 @@ from typing import Dict, Optional
 import torch
 import torch.nn.functional as F
 
+from oracle.encodec_oracle import fold
+
 
 def _cfg_get(cfg, name):
     return cfg[name] if isinstance(cfg, dict) else getattr(cfg, name)
@@ -57,41 +59,43 @@ def res_unit(x, W, p: str, dilation: int):
     return x + y
 
 
-def encoder(cfg, W, x, taps: Optional[dict] = None):
-    """[HF]:444-474 DacEncoder: conv k7 pad 3; per stride s: 3 residual units (dilations 1,3,9), snake,
-    conv k=2s stride s pad ceil(s/2) ([HF]:212-233); snake; conv k3 pad 1.  x [B,1,T] -> [B,hidden,N]."""
-    def tap(name, v):
-        if taps is not None:
-            taps[name] = v
-        return v
-
-    x = tap("encoder.conv1", F.conv1d(x, W["encoder.conv1.weight"], W["encoder.conv1.bias"], padding=3))
+def encoder_layers(cfg, W):
+    """[HF]:444-474 DacEncoder as an ordered list of (tap_name, fn): conv k7 pad 3; per stride s: 3 residual units
+    (dilations 1,3,9), snake + conv k=2s stride s pad ceil(s/2) ([HF]:212-233); snake + conv k3 pad 1.  fn maps the previous
+    module output [B,C,L] (the first: the signal [B,1,T]) to this module's, in the dtype of W."""
+    layers = [("encoder.conv1", lambda x: F.conv1d(x, W["encoder.conv1.weight"], W["encoder.conv1.bias"], padding=3))]
     for i, s in enumerate(_cfg_get(cfg, "downsampling_ratios")):
         p = f"encoder.block.{i}"
         for u, d in enumerate(_cfg_get(cfg, "dilations"), start=1):
-            x = tap(f"{p}.res_unit{u}", res_unit(x, W, f"{p}.res_unit{u}", d))
-        x = tap(f"{p}.conv1", F.conv1d(snake(x, W[p + ".snake1.alpha"]), W[p + ".conv1.weight"], W[p + ".conv1.bias"],
-                                       stride=s, padding=math.ceil(s / 2)))
-    return tap("encoder.conv2", F.conv1d(snake(x, W["encoder.snake1.alpha"]), W["encoder.conv2.weight"], W["encoder.conv2.bias"], padding=1))
+            layers.append((f"{p}.res_unit{u}", lambda x, p=p, u=u, d=d: res_unit(x, W, f"{p}.res_unit{u}", d)))
+        layers.append((f"{p}.conv1", lambda x, p=p, s=s: F.conv1d(snake(x, W[p + ".snake1.alpha"]), W[p + ".conv1.weight"], W[p + ".conv1.bias"],
+                                                                  stride=s, padding=math.ceil(s / 2))))
+    layers.append(("encoder.conv2", lambda x: F.conv1d(snake(x, W["encoder.snake1.alpha"]), W["encoder.conv2.weight"], W["encoder.conv2.bias"], padding=1)))
+    return layers
+
+
+def decoder_layers(cfg, W):
+    """[HF]:407-441 DacDecoder as an ordered list of (tap_name, fn): conv k7 pad 3; per stride s: snake + transposed conv
+    k=2s stride s pad ceil(s/2), 3 residual units ([HF]:236-264); snake + conv k7 pad 3 + tanh.  The first fn takes z_q [B,hidden,N]."""
+    layers = [("decoder.conv1", lambda z: F.conv1d(z, W["decoder.conv1.weight"], W["decoder.conv1.bias"], padding=3))]
+    for i, s in enumerate(_cfg_get(cfg, "upsampling_ratios")):
+        p = f"decoder.block.{i}"
+        layers.append((f"{p}.conv_t1", lambda x, p=p, s=s: F.conv_transpose1d(snake(x, W[p + ".snake1.alpha"]), W[p + ".conv_t1.weight"], W[p + ".conv_t1.bias"],
+                                                                              stride=s, padding=math.ceil(s / 2))))
+        for u, d in enumerate(_cfg_get(cfg, "dilations"), start=1):
+            layers.append((f"{p}.res_unit{u}", lambda x, p=p, u=u, d=d: res_unit(x, W, f"{p}.res_unit{u}", d)))
+    layers.append(("decoder.conv2", lambda x: torch.tanh(F.conv1d(snake(x, W["decoder.snake1.alpha"]), W["decoder.conv2.weight"], W["decoder.conv2.bias"], padding=3))))
+    return layers
+
+
+def encoder(cfg, W, x, taps: Optional[dict] = None):
+    """[HF]:444-474 DacEncoder.  x [B,1,T] -> [B,hidden,N]."""
+    return fold(encoder_layers(cfg, W), x, taps)
 
 
 def decoder(cfg, W, z, taps: Optional[dict] = None):
-    """[HF]:407-441 DacDecoder: conv k7 pad 3; per stride s: snake, transposed conv k=2s stride s pad
-    ceil(s/2), 3 residual units ([HF]:236-264); snake; conv k7 pad 3; tanh.  z [B,hidden,N] -> [B,1,T']."""
-    def tap(name, v):
-        if taps is not None:
-            taps[name] = v
-        return v
-
-    x = tap("decoder.conv1", F.conv1d(z, W["decoder.conv1.weight"], W["decoder.conv1.bias"], padding=3))
-    for i, s in enumerate(_cfg_get(cfg, "upsampling_ratios")):
-        p = f"decoder.block.{i}"
-        x = tap(f"{p}.conv_t1", F.conv_transpose1d(snake(x, W[p + ".snake1.alpha"]), W[p + ".conv_t1.weight"], W[p + ".conv_t1.bias"],
-                                                   stride=s, padding=math.ceil(s / 2)))
-        for u, d in enumerate(_cfg_get(cfg, "dilations"), start=1):
-            x = tap(f"{p}.res_unit{u}", res_unit(x, W, f"{p}.res_unit{u}", d))
-    x = F.conv1d(snake(x, W["decoder.snake1.alpha"]), W["decoder.conv2.weight"], W["decoder.conv2.bias"], padding=3)
-    return tap("decoder.conv2", torch.tanh(x))
+    """[HF]:407-441 DacDecoder.  z [B,hidden,N] -> [B,1,T']."""
+    return fold(decoder_layers(cfg, W), z, taps)
 
 
 # --------------------------------------------------------------------------------------------

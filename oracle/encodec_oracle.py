@@ -131,50 +131,72 @@ def lstm_skip(x, W, p: str, num_layers: int, explicit: bool = False):
     return (y + xt).permute(1, 2, 0)
 
 
-def encoder(cfg, W, x, taps: Optional[dict] = None, explicit_lstm: bool = False):
-    """[HF]:285-313 EncodecEncoder.  x [B,1,T] -> [B,hidden,N]."""
+def fold(layers, x, taps: Optional[dict] = None, untapped: Sequence[str] = ()):
+    """Run an ordered list of (tap_name, fn) on x; every output but those named in `untapped` is recorded in `taps`."""
+    for name, fn in layers:
+        x = fn(x)
+        if taps is not None and name not in untapped:
+            taps[name] = x
+    return x
+
+
+def encoder_layers(cfg, W, explicit_lstm: bool = False):
+    """[HF]:285-313 EncodecEncoder as an ordered list of (tap_name, fn): fn maps the previous module output
+    ([B,C,L]; the first one takes the signal [B,1,T]) to this module's, in the dtype of W.  The ELU modules have no
+    entry of their own: each conv that follows one applies it.  The last entry (the final conv) is the encoder's output."""
     ratios = list(_cfg_get(cfg, "upsampling_ratios"))
     p = "encoder.layers."
-    h = conv1d_causal(x, W[p + "0.conv.weight"], W[p + "0.conv.bias"])
-    if taps is not None:
-        taps["enc0"] = h
+
+    def conv(j, stride=1, elu=True):
+        w, b = W[f"{p}{j}.conv.weight"], W[f"{p}{j}.conv.bias"]
+        return lambda h: conv1d_causal(F.elu(h) if elu else h, w, b, stride=stride)
+
+    layers = [("enc0", conv(0, elu=False))]
     i = 1
     for r in reversed(ratios):
-        h = resblock(h, W, f"{p}{i}")
-        if taps is not None:
-            taps[f"enc{i}"] = h
-        h = conv1d_causal(F.elu(h), W[f"{p}{i + 2}.conv.weight"], W[f"{p}{i + 2}.conv.bias"], stride=r)
-        if taps is not None:
-            taps[f"enc{i + 2}"] = h
+        layers.append((f"enc{i}", lambda h, i=i: resblock(h, W, f"{p}{i}")))
+        layers.append((f"enc{i + 2}", conv(i + 2, stride=r)))
         i += 3
-    h = lstm_skip(h, W, f"{p}{i}.lstm", _cfg_get(cfg, "num_lstm_layers"), explicit_lstm)
-    if taps is not None:
-        taps[f"enc{i}"] = h
-    h = conv1d_causal(F.elu(h), W[f"{p}{i + 2}.conv.weight"], W[f"{p}{i + 2}.conv.bias"])
-    return h
+    layers.append((f"enc{i}", lambda h, i=i: lstm_skip(h, W, f"{p}{i}.lstm", _cfg_get(cfg, "num_lstm_layers"), explicit_lstm)))
+    layers.append((f"enc{i + 2}", conv(i + 2)))
+    return layers
+
+
+def decoder_layers(cfg, W, explicit_lstm: bool = False):
+    """[HF]:316-347 EncodecDecoder as an ordered list of (tap_name, fn), as `encoder_layers`; the first fn takes the
+    dequantised features [B,hidden,N], the last entry (the final conv) gives [B,1,N*hop]."""
+    ratios = list(_cfg_get(cfg, "upsampling_ratios"))
+    p = "decoder.layers."
+
+    def conv(j, elu=True):
+        w, b = W[f"{p}{j}.conv.weight"], W[f"{p}{j}.conv.bias"]
+        return lambda h: conv1d_causal(F.elu(h) if elu else h, w, b)
+
+    def convtr(j, r):
+        w, b = W[f"{p}{j}.conv.weight"], W[f"{p}{j}.conv.bias"]
+        return lambda h: convtr1d_causal(F.elu(h), w, b, r)
+
+    layers = [("dec0", conv(0, elu=False)),
+              ("dec1", lambda h: lstm_skip(h, W, p + "1.lstm", _cfg_get(cfg, "num_lstm_layers"), explicit_lstm))]
+    i = 2
+    for r in ratios:
+        layers.append((f"dec{i + 1}", convtr(i + 1, r)))
+        layers.append((f"dec{i + 2}", lambda h, i=i: resblock(h, W, f"{p}{i + 2}")))
+        i += 3
+    layers.append((f"dec{i + 1}", conv(i + 1)))
+    return layers
+
+
+def encoder(cfg, W, x, taps: Optional[dict] = None, explicit_lstm: bool = False):
+    """[HF]:285-313 EncodecEncoder.  x [B,1,T] -> [B,hidden,N].  (`taps` gets every module output but the last.)"""
+    layers = encoder_layers(cfg, W, explicit_lstm)
+    return fold(layers, x, taps, untapped=(layers[-1][0],))
 
 
 def decoder(cfg, W, z, taps: Optional[dict] = None, explicit_lstm: bool = False):
-    """[HF]:316-347 EncodecDecoder.  z [B,hidden,N] -> [B,1,N*hop]."""
-    ratios = list(_cfg_get(cfg, "upsampling_ratios"))
-    p = "decoder.layers."
-    h = conv1d_causal(z, W[p + "0.conv.weight"], W[p + "0.conv.bias"])
-    if taps is not None:
-        taps["dec0"] = h
-    h = lstm_skip(h, W, p + "1.lstm", _cfg_get(cfg, "num_lstm_layers"), explicit_lstm)
-    if taps is not None:
-        taps["dec1"] = h
-    i = 2
-    for r in ratios:
-        h = convtr1d_causal(F.elu(h), W[f"{p}{i + 1}.conv.weight"], W[f"{p}{i + 1}.conv.bias"], r)
-        if taps is not None:
-            taps[f"dec{i + 1}"] = h
-        h = resblock(h, W, f"{p}{i + 2}")
-        if taps is not None:
-            taps[f"dec{i + 2}"] = h
-        i += 3
-    h = conv1d_causal(F.elu(h), W[f"{p}{i + 1}.conv.weight"], W[f"{p}{i + 1}.conv.bias"])
-    return h
+    """[HF]:316-347 EncodecDecoder.  z [B,hidden,N] -> [B,1,N*hop].  (`taps` gets every module output but the last.)"""
+    layers = decoder_layers(cfg, W, explicit_lstm)
+    return fold(layers, z, taps, untapped=(layers[-1][0],))
 
 
 def codebooks(W, K: int) -> List[torch.Tensor]:

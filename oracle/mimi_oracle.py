@@ -26,6 +26,8 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
+from oracle.encodec_oracle import fold
+
 
 def _cfg_get(cfg, name):
     return cfg[name] if isinstance(cfg, dict) else getattr(cfg, name)
@@ -82,44 +84,52 @@ def resblock(x, W, p: str):
     return x + h
 
 
-def encoder(cfg, W, x, taps: Optional[dict] = None):
-    """[HF]:444-492 MimiEncoder: x [B,1,T] -> [B,hidden,T/prod(ratios)]."""
+def _conv(W, p: str, stride: int = 1, elu: bool = True):
+    w, b = W[p + ".conv.weight"], W[p + ".conv.bias"]
+    return lambda x: conv1d_causal(F.elu(x) if elu else x, w, b, stride=stride)
+
+
+def encoder_layers(cfg, W):
+    """[HF]:444-492 MimiEncoder as an ordered list of (tap_name, fn): fn maps the previous module output [B,C,L] (the
+    first: the signal [B,1,T]) to this module's, in the dtype of W.  ELU modules have no entry: the conv after one applies it."""
     ratios = list(_cfg_get(cfg, "upsampling_ratios"))
-
-    def tap(name, v):
-        if taps is not None:
-            taps[name] = v
-        return v
-
-    x = tap("encoder.layers.0", conv1d_causal(x, W["encoder.layers.0.conv.weight"], W["encoder.layers.0.conv.bias"]))
+    layers = [("encoder.layers.0", _conv(W, "encoder.layers.0", elu=False))]
     i = 1
     for r in reversed(ratios):
-        x = tap(f"encoder.layers.{i}", resblock(x, W, f"encoder.layers.{i}"))
-        p = f"encoder.layers.{i + 2}.conv"
-        x = tap(f"encoder.layers.{i + 2}", conv1d_causal(F.elu(x), W[p + ".weight"], W[p + ".bias"], stride=r))
+        layers.append((f"encoder.layers.{i}", lambda x, i=i: resblock(x, W, f"encoder.layers.{i}")))
+        layers.append((f"encoder.layers.{i + 2}", _conv(W, f"encoder.layers.{i + 2}", stride=r)))
         i += 3
-    p = f"encoder.layers.{i + 1}.conv"
-    return tap(f"encoder.layers.{i + 1}", conv1d_causal(F.elu(x), W[p + ".weight"], W[p + ".bias"]))
+    layers.append((f"encoder.layers.{i + 1}", _conv(W, f"encoder.layers.{i + 1}")))
+    return layers
+
+
+def decoder_layers(cfg, W):
+    """[HF]:931-961 MimiDecoder as an ordered list of (tap_name, fn), as `encoder_layers`; the first fn takes the decoder
+    transformer's output [B,hidden,N'], the last gives [B,1,N'*prod(ratios)]."""
+    ratios = list(_cfg_get(cfg, "upsampling_ratios"))
+
+    def convtr(p, r):
+        w, b = W[p + ".conv.weight"], W[p + ".conv.bias"]
+        return lambda x: convtr1d_causal(F.elu(x), w, b, r)
+
+    layers = [("decoder.layers.0", _conv(W, "decoder.layers.0", elu=False))]
+    i = 1
+    for r in ratios:
+        layers.append((f"decoder.layers.{i + 1}", convtr(f"decoder.layers.{i + 1}", r)))
+        layers.append((f"decoder.layers.{i + 2}", lambda x, i=i: resblock(x, W, f"decoder.layers.{i + 2}")))
+        i += 3
+    layers.append((f"decoder.layers.{i + 1}", _conv(W, f"decoder.layers.{i + 1}")))
+    return layers
+
+
+def encoder(cfg, W, x, taps: Optional[dict] = None):
+    """[HF]:444-492 MimiEncoder: x [B,1,T] -> [B,hidden,T/prod(ratios)]."""
+    return fold(encoder_layers(cfg, W), x, taps)
 
 
 def decoder(cfg, W, z, taps: Optional[dict] = None):
     """[HF]:931-961 MimiDecoder: z [B,hidden,N'] -> [B,1,N'*prod(ratios)]."""
-    ratios = list(_cfg_get(cfg, "upsampling_ratios"))
-
-    def tap(name, v):
-        if taps is not None:
-            taps[name] = v
-        return v
-
-    x = tap("decoder.layers.0", conv1d_causal(z, W["decoder.layers.0.conv.weight"], W["decoder.layers.0.conv.bias"]))
-    i = 1
-    for r in ratios:
-        p = f"decoder.layers.{i + 1}.conv"
-        x = tap(f"decoder.layers.{i + 1}", convtr1d_causal(F.elu(x), W[p + ".weight"], W[p + ".bias"], r))
-        x = tap(f"decoder.layers.{i + 2}", resblock(x, W, f"decoder.layers.{i + 2}"))
-        i += 3
-    p = f"decoder.layers.{i + 1}.conv"
-    return tap(f"decoder.layers.{i + 1}", conv1d_causal(F.elu(x), W[p + ".weight"], W[p + ".bias"]))
+    return fold(decoder_layers(cfg, W), z, taps)
 
 
 # --------------------------------------------------------------------------------------------
@@ -127,12 +137,12 @@ def decoder(cfg, W, z, taps: Optional[dict] = None):
 # --------------------------------------------------------------------------------------------
 
 
-def rope_tables(cfg, T: int, dtype):
-    """[HF]:528-567 MimiRotaryEmbedding ("default" rope): inv_freq = 1 / theta^(2i/d) and the
-    position products are evaluated in fp32 whatever the model dtype, then cast."""
+def rope_tables(cfg, T: int, dtype, pos0: int = 0):
+    """[HF]:528-567 MimiRotaryEmbedding ("default" rope) for positions pos0 .. pos0+T-1: inv_freq = 1 / theta^(2i/d) and
+    the position products are evaluated in fp32 whatever the model dtype, then cast."""
     d = _cfg_get(cfg, "head_dim")
     inv_freq = 1.0 / (_cfg_get(cfg, "rope_theta") ** (torch.arange(0, d, 2, dtype=torch.float) / d))
-    freqs = (inv_freq[:, None] @ torch.arange(T, dtype=torch.float)[None, :]).transpose(0, 1)  # [T, d/2]
+    freqs = (inv_freq[:, None] @ torch.arange(pos0, pos0 + T, dtype=torch.float)[None, :]).transpose(0, 1)  # [T, d/2]
     emb = torch.cat((freqs, freqs), dim=-1)
     return emb.cos().to(dtype), emb.sin().to(dtype)
 
@@ -142,37 +152,55 @@ def _rotate_half(x):
     return torch.cat((-x[..., h:], x[..., :h]), dim=-1)
 
 
-def transformer(cfg, W, x, part: str, taps: Optional[dict] = None):
-    """[HF]:729-928 MimiTransformerModel on x [B,T,hidden]: per layer
+def transformer_layer(cfg, W, p: str, x, pos0: int = 0):
+    """One [HF]:729-928 layer (weights under prefix p) on x [B,T,hidden] whose first row sits at position pos0:
         x = x + scale_a * o_proj(attn(LN(x)));   x = x + scale_m * fc2(gelu(fc1(LN(x))))
     attention ([HF]:657-727): RoPE on q,k, causal sliding-window mask (key j visible to query i iff
     j <= i and i - j < sliding_window), softmax in fp32, scaling 1/sqrt(head_dim)."""
     B, T, H = x.shape
     nh, hd = _cfg_get(cfg, "num_attention_heads"), _cfg_get(cfg, "head_dim")
     eps, win = _cfg_get(cfg, "norm_eps"), _cfg_get(cfg, "sliding_window")
-    cos, sin = rope_tables(cfg, T, x.dtype)
+    cos, sin = rope_tables(cfg, T, x.dtype, pos0)
     i = torch.arange(T)
     visible = (i[None, :] <= i[:, None]) & (i[:, None] - i[None, :] < win)
     bias = torch.zeros(T, T, dtype=x.dtype).masked_fill(~visible, float("-inf"))
-    for l in range(_cfg_get(cfg, "num_hidden_layers")):
-        p = f"{part}.layers.{l}"
-        h = F.layer_norm(x, (H,), W[p + ".input_layernorm.weight"], W[p + ".input_layernorm.bias"], eps)
-        q = F.linear(h, W[p + ".self_attn.q_proj.weight"]).view(B, T, nh, hd).transpose(1, 2)
-        k = F.linear(h, W[p + ".self_attn.k_proj.weight"]).view(B, T, nh, hd).transpose(1, 2)
-        v = F.linear(h, W[p + ".self_attn.v_proj.weight"]).view(B, T, nh, hd).transpose(1, 2)
-        q = q * cos + _rotate_half(q) * sin
-        k = k * cos + _rotate_half(k) * sin
-        a = torch.matmul(q, k.transpose(2, 3)) * (1.0 / math.sqrt(hd)) + bias
-        a = F.softmax(a, dim=-1, dtype=torch.float32 if x.dtype == torch.float32 else x.dtype).to(x.dtype)
-        o = torch.matmul(a, v).transpose(1, 2).reshape(B, T, nh * hd)
-        o = F.linear(o, W[p + ".self_attn.o_proj.weight"])
-        x = x + W[p + ".self_attn_layer_scale.scale"] * o
-        h = F.layer_norm(x, (H,), W[p + ".post_attention_layernorm.weight"], W[p + ".post_attention_layernorm.bias"], eps)
-        h = F.linear(F.gelu(F.linear(h, W[p + ".mlp.fc1.weight"])), W[p + ".mlp.fc2.weight"])
-        x = x + W[p + ".mlp_layer_scale.scale"] * h
-        if taps is not None:
-            taps[p] = x
-    return x
+    h = F.layer_norm(x, (H,), W[p + ".input_layernorm.weight"], W[p + ".input_layernorm.bias"], eps)
+    q = F.linear(h, W[p + ".self_attn.q_proj.weight"]).view(B, T, nh, hd).transpose(1, 2)
+    k = F.linear(h, W[p + ".self_attn.k_proj.weight"]).view(B, T, nh, hd).transpose(1, 2)
+    v = F.linear(h, W[p + ".self_attn.v_proj.weight"]).view(B, T, nh, hd).transpose(1, 2)
+    q = q * cos + _rotate_half(q) * sin
+    k = k * cos + _rotate_half(k) * sin
+    a = torch.matmul(q, k.transpose(2, 3)) * (1.0 / math.sqrt(hd)) + bias
+    a = F.softmax(a, dim=-1, dtype=torch.float32 if x.dtype == torch.float32 else x.dtype).to(x.dtype)
+    o = torch.matmul(a, v).transpose(1, 2).reshape(B, T, nh * hd)
+    o = F.linear(o, W[p + ".self_attn.o_proj.weight"])
+    x = x + W[p + ".self_attn_layer_scale.scale"] * o
+    h = F.layer_norm(x, (H,), W[p + ".post_attention_layernorm.weight"], W[p + ".post_attention_layernorm.bias"], eps)
+    h = F.linear(F.gelu(F.linear(h, W[p + ".mlp.fc1.weight"])), W[p + ".mlp.fc2.weight"])
+    return x + W[p + ".mlp_layer_scale.scale"] * h
+
+
+def transformer_layers(cfg, W, part: str):
+    """The layers of `part` ("encoder_transformer" / "decoder_transformer") as an ordered list of (tap_name, fn);
+    fn(x [B,T,hidden], pos0=0) -> [B,T,hidden], pos0 the position of x's first row (RoPE and the window count from it)."""
+    return [(f"{part}.layers.{l}", lambda x, pos0=0, l=l: transformer_layer(cfg, W, f"{part}.layers.{l}", x, pos0))
+            for l in range(_cfg_get(cfg, "num_hidden_layers"))]
+
+
+def transformer(cfg, W, x, part: str, taps: Optional[dict] = None):
+    """[HF]:729-928 MimiTransformerModel on x [B,T,hidden]."""
+    return fold(transformer_layers(cfg, W, part), x, taps)
+
+
+def downsample(cfg, W):
+    """(tap_name, fn): the replicate-padded stride-`resample_stride` conv without bias ([HF]:1199-1208) on [B,hidden,T']."""
+    return "downsample", lambda x: conv1d_causal(x, W["downsample.conv.weight"], None, stride=_cfg_get(cfg, "resample_stride"), pad_mode="replicate")
+
+
+def upsample(cfg, W):
+    """(tap_name, fn): the depthwise transposed conv, stride `resample_stride`, no bias, on the quantiser's output [B,hidden,N]."""
+    w = W["upsample.conv.weight"]
+    return "upsample", lambda z: convtr1d_causal(z, w, None, _cfg_get(cfg, "resample_stride"), groups=w.shape[0])
 
 
 # --------------------------------------------------------------------------------------------
@@ -275,10 +303,7 @@ def embeddings(cfg, W, sig, taps: Optional[dict] = None):
     no effect on Mimi's outputs."""
     x = encoder(cfg, W, sig[:, None].to(_dtype(W)), taps)
     x = transformer(cfg, W, x.transpose(1, 2), "encoder_transformer", taps).transpose(1, 2)
-    z = conv1d_causal(x, W["downsample.conv.weight"], None, stride=_cfg_get(cfg, "resample_stride"), pad_mode="replicate")
-    if taps is not None:
-        taps["downsample"] = z
-    return z
+    return fold([downsample(cfg, W)], x, taps)
 
 
 def sig_to_feats(cfg, W, sig, length=None, taps=None):
@@ -313,10 +338,7 @@ def toks_to_sig(cfg, W, toks, taps=None):
     z = rvq_decode(cfg, W, toks.movedim(-1, -2))
     if taps is not None:
         taps["quantizer.decode"] = z
-    w = W["upsample.conv.weight"]
-    x = convtr1d_causal(z, w, None, _cfg_get(cfg, "resample_stride"), groups=w.shape[0])
-    if taps is not None:
-        taps["upsample"] = x
+    x = fold([upsample(cfg, W)], z, taps)
     x = transformer(cfg, W, x.transpose(1, 2), "decoder_transformer", taps).transpose(1, 2)
     return decoder(cfg, W, x, taps)[:, 0]
 

@@ -38,7 +38,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn.functional as F
 
-from oracle.encodec_oracle import lstm_skip
+from oracle.encodec_oracle import fold, lstm_skip
 
 
 def cast_weights(sd: Dict[str, torch.Tensor], dtype=torch.float32) -> Dict[str, torch.Tensor]:
@@ -88,26 +88,31 @@ def resblock(x, W, p: str):
     return sconv1d(x, W[p + ".shortcut.conv.conv.weight"], W[p + ".shortcut.conv.conv.bias"]) + h
 
 
-def encoder(cfg, W, x, taps: Optional[dict] = None):
-    """SEANetEncoder: x [B,1,T] -> [B,dimension,N]."""
+def encoder_layers(cfg, W):
+    """SEANetEncoder as an ordered list of (tap_name, fn): fn maps the previous module output [B,C,L] (the first: the
+    signal [B,1,T]) to this module's, in the dtype of W, with the centred (non-causal) reflect padding of `sconv1d`.
+    The last entry (the final conv) is the encoder's output."""
     p = "feature_extractor.encodec.encoder.model."
-    h = sconv1d(x, W[p + "0.conv.conv.weight"], W[p + "0.conv.conv.bias"])
-    if taps is not None:
-        taps["enc0"] = h
+
+    def conv(j, stride=1, elu=True):
+        w, b = W[f"{p}{j}.conv.conv.weight"], W[f"{p}{j}.conv.conv.bias"]
+        return lambda h: sconv1d(F.elu(h) if elu else h, w, b, stride=stride)
+
+    layers = [("enc0", conv(0, elu=False))]
     i = 1
     for r in reversed(cfg.ratios):
-        h = resblock(h, W, f"{p}{i}")
-        if taps is not None:
-            taps[f"enc{i}"] = h
-        h = sconv1d(F.elu(h), W[f"{p}{i + 2}.conv.conv.weight"], W[f"{p}{i + 2}.conv.conv.bias"], stride=r)
-        if taps is not None:
-            taps[f"enc{i + 2}"] = h
+        layers.append((f"enc{i}", lambda h, i=i: resblock(h, W, f"{p}{i}")))
+        layers.append((f"enc{i + 2}", conv(i + 2, stride=r)))
         i += 3
-    h = lstm_skip(h, W, f"{p}{i}.lstm", cfg.num_lstm_layers)
-    if taps is not None:
-        taps[f"enc{i}"] = h
-    h = sconv1d(F.elu(h), W[f"{p}{i + 2}.conv.conv.weight"], W[f"{p}{i + 2}.conv.conv.bias"])
-    return h
+    layers.append((f"enc{i}", lambda h, i=i: lstm_skip(h, W, f"{p}{i}.lstm", cfg.num_lstm_layers)))
+    layers.append((f"enc{i + 2}", conv(i + 2)))
+    return layers
+
+
+def encoder(cfg, W, x, taps: Optional[dict] = None):
+    """SEANetEncoder: x [B,1,T] -> [B,dimension,N].  (`taps` gets every module output but the last.)"""
+    layers = encoder_layers(cfg, W)
+    return fold(layers, x, taps, untapped=(layers[-1][0],))
 
 
 # --------------------------------------------------------------------------------------------- quantiser
@@ -170,37 +175,34 @@ def convnext(x, W, p: str, cond: int):
     return x + h.transpose(1, 2)
 
 
+def backbone_layers(cfg, W):
+    """VocosBackbone as an ordered list of (tap_name, fn), every tensor in [B,C,N] (the two norms over the channel
+    dimension transpose inside their fn); the first fn takes the features [B,dimension,N]."""
+    g, cond = cfg.num_groups, cfg.bandwidth_id
+    layers = [("embed", lambda x: F.conv1d(x, W["backbone.embed.weight"], W["backbone.embed.bias"], padding=3))]
+    for i in (0, 1):
+        layers.append((f"pos{i}", lambda x, i=i: resnet_block(x, W, f"backbone.pos_net.{i}", g)))
+    layers.append(("pos2", lambda x: attn_block(x, W, "backbone.pos_net.2", g)))
+    for i in (3, 4):
+        layers.append((f"pos{i}", lambda x, i=i: resnet_block(x, W, f"backbone.pos_net.{i}", g)))
+    layers.append(("pos5", lambda x: _gn(x, W, "backbone.pos_net.5", g)))
+    layers.append(("norm", lambda x: _adanorm(x.transpose(1, 2), W, "backbone.norm", cond).transpose(1, 2)))
+    for l in range(cfg.num_layers):
+        layers.append((f"cnx{l}", lambda x, l=l: convnext(x, W, f"backbone.convnext.{l}", cond)))
+    layers.append(("final", lambda x: F.layer_norm(x.transpose(1, 2), (x.shape[1],), W["backbone.final_layer_norm.weight"],
+                                                   W["backbone.final_layer_norm.bias"], eps=1e-6).transpose(1, 2)))
+    return layers
+
+
+def decoder_layers(cfg, W):
+    """The decode path from the quantised features [B,dimension,N]: `backbone_layers` and, last, ("sig", the ISTFT head)
+    taking the backbone's output in [B,C,N] and giving the waveform [B, N*hop]."""
+    return backbone_layers(cfg, W) + [("sig", lambda x: head(cfg, W, x.transpose(1, 2)))]
+
+
 def backbone(cfg, W, feats, taps: Optional[dict] = None):
     """VocosBackbone.forward: feats [B,dimension,N] -> [B,N,backbone_dim]."""
-    g, cond = cfg.num_groups, cfg.bandwidth_id
-    x = F.conv1d(feats, W["backbone.embed.weight"], W["backbone.embed.bias"], padding=3)
-    if taps is not None:
-        taps["embed"] = x
-    for i in (0, 1):
-        x = resnet_block(x, W, f"backbone.pos_net.{i}", g)
-        if taps is not None:
-            taps[f"pos{i}"] = x
-    x = attn_block(x, W, "backbone.pos_net.2", g)
-    if taps is not None:
-        taps["pos2"] = x
-    for i in (3, 4):
-        x = resnet_block(x, W, f"backbone.pos_net.{i}", g)
-        if taps is not None:
-            taps[f"pos{i}"] = x
-    x = _gn(x, W, "backbone.pos_net.5", g)
-    if taps is not None:
-        taps["pos5"] = x
-    x = _adanorm(x.transpose(1, 2), W, "backbone.norm", cond).transpose(1, 2)
-    if taps is not None:
-        taps["norm"] = x
-    for l in range(cfg.num_layers):
-        x = convnext(x, W, f"backbone.convnext.{l}", cond)
-        if taps is not None:
-            taps[f"cnx{l}"] = x
-    x = F.layer_norm(x.transpose(1, 2), (x.shape[1],), W["backbone.final_layer_norm.weight"], W["backbone.final_layer_norm.bias"], eps=1e-6)
-    if taps is not None:
-        taps["final"] = x.transpose(1, 2)
-    return x
+    return fold(backbone_layers(cfg, W), feats, taps).transpose(1, 2)
 
 
 def istft_same(spec, n_fft: int, hop: int, window):

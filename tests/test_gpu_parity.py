@@ -16,6 +16,7 @@ import torch
 from conftest import GOLDEN_DIR
 from golden_cases import CASES, REC_STRIDE, make_input, noise
 from test_oracle_golden import TAU, tokens_match_up_to_ties
+import layer_cases as LC
 import parity_record
 
 pytestmark = pytest.mark.gpu
@@ -277,15 +278,24 @@ def test_split_operand_and_exact_product_kernels_agree(checkpoints, golden, monk
     assert bad == 0
 
 
-FULL_ENC_TAPS = ["enc0", "enc1", "enc3", "enc4", "enc6", "enc7", "enc9", "enc10", "enc12", "enc13"]
-FULL_DEC_TAPS = ["dec0", "dec1", "dec3", "dec4", "dec6", "dec7", "dec9", "dec10", "dec12", "dec13"]
+def _full_taps(direction):
+    from audiocodecs_amd.config import ENCODEC_24KHZ
+
+    return [t.name for t in LC.taps_of("encodec", ENCODEC_24KHZ, direction)]
+
+
+FULL_ENC_TAPS = _full_taps("encode")     # (tests/test_fused_chains_gpu.py reads these)
+FULL_DEC_TAPS = _full_taps("decode")
 
 
 def test_every_module_output_full_config_production_kernels(codecs, checkpoints):
-    """FULL architecture through the production kernels (enc_stream, rb_stream6, rb_stream128m, the tap-GEMMs, the persistent
-    LSTM, dec_stream): arming the capture hook does not change kernel selection; every module output of a 1 s clip
-    against the oracle's taps (the oracle is pinned to the reference's hooks on the tiny config and to its end-to-end
-    outputs on this one).  A localized error shows up at its layer, not as a vague feature RMS."""
+    """FULL architecture through the production kernels: enc_stream (stem, first residual block and first down-sampler as one
+    chain), rb_stream6 / rb_stream128m (the 64- and 128-channel residual blocks), rb_fused6 (the 256-channel one), the tap-GEMMs,
+    the persistent LSTM (lstm_persist16) and dec_stream (last up-sampler, last residual block and head).  Arming the capture hook
+    does not change kernel selection on this path -- the chains write their inner module outputs themselves while it is armed
+    (tests/test_layer_isolation_gpu.py::test_production_kernels_run_under_the_hook pins the names).  Every module output of a 1 s
+    clip against the oracle's taps (the oracle is pinned to the reference's hooks on the tiny config and to its end-to-end outputs on
+    this one); the tap order comes from tests/layer_cases.py.  A localized error shows up at its layer, not as a vague feature RMS."""
     from oracle import encodec_oracle as O
 
     cfg, sd = checkpoints("full", 0)
@@ -301,26 +311,20 @@ def test_every_module_output_full_config_production_kernels(codecs, checkpoints)
     nat = next(iter(codec._natives.values()))
     assert nat.lib.ac_lstm_status(nat.h) == 1   # the persistent LSTM is what runs
     _, flat = capture(codec, lambda: codec.sig_to_toks(sig.cuda()), 1 << 26)
-    off = 0
     worst = {}
-    for tap in FULL_ENC_TAPS:
-        g = taps[tap].numpy()  # [B,C,L]
-        n = g.size
-        got = flat[off : off + n].reshape(g.shape[0], g.shape[2], g.shape[1]).transpose(0, 2, 1)
+    enc = LC.taps_of("encodec", cfg, "encode")
+    got_of = LC.split_capture(flat, enc, lambda t: taps[t.name].shape)
+    for tap in (t.name for t in enc):
+        g, got = taps[tap].numpy(), got_of[tap]  # [B,C,L]
         worst[tap] = float(np.abs(got - g).max() / max(1e-30, np.abs(g).max()))
         np.testing.assert_allclose(got, g, atol=5e-6 * max(1.0, float(np.abs(g).max())), rtol=2e-5, err_msg=tap)
-        off += n
-    assert off == flat.size
     rec, flat = capture(codec, lambda: codec.toks_to_sig(otoks.cuda()), 1 << 26)
-    off = 0
-    for tap in FULL_DEC_TAPS:
-        g = dtaps[tap].numpy()
-        n = g.size
-        got = flat[off : off + n].reshape(g.shape[0], g.shape[2], g.shape[1]).transpose(0, 2, 1)
+    dec = LC.taps_of("encodec", cfg, "decode")
+    got_of = LC.split_capture(flat, dec, lambda t: dtaps[t.name].shape)
+    for tap in (t.name for t in dec):
+        g, got = dtaps[tap].numpy(), got_of[tap]
         worst[tap] = float(np.abs(got - g).max() / max(1e-30, np.abs(g).max()))
         np.testing.assert_allclose(got, g, atol=5e-6 * max(1.0, float(np.abs(g).max())), rtol=2e-5, err_msg=tap)
-        off += n
-    assert off == flat.size
     parity_record.record("encodec", "full_config_module_taps", worst_rel_err_per_tap=worst,
                          waveform_rms_err=rms((rec.cpu() - orec).numpy()))
     assert rms((rec.cpu() - orec).numpy()) < 1e-5

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import layer_cases as LC
 import parity_record
 from conftest import GOLDEN_DIR
 from golden_cases import noise
@@ -59,16 +60,13 @@ def capture(codec, fn, nfloats=1 << 25):
 
 def check_taps(flat, names, gold_of, atol, rtol=2e-5):
     """flat: captured module outputs, each [B][L][C]; gold_of(name) -> [B,C,L] array."""
-    off, worst = 0, {}
+    worst = {}
+    got_of = LC.split_capture(flat, [LC.Tap(n, n, "BCL", LC.INPUT) for n in names], lambda t: gold_of(t.name).shape)
     for tap in names:
-        g = gold_of(tap)
-        n = g.size
-        got = flat[off : off + n].reshape(g.shape[0], g.shape[2], g.shape[1]).transpose(0, 2, 1)
+        g, got = gold_of(tap), got_of[tap]
         scale = max(1.0, float(np.abs(g).max()))
         worst[tap] = float(np.abs(got - g).max() / scale)
         np.testing.assert_allclose(got, g, atol=atol * scale, rtol=rtol, err_msg=tap)
-        off += n
-    assert off == flat.size
     return worst
 
 
@@ -113,9 +111,9 @@ def test_every_module_output_full_config_production_kernels(codecs, wavtok_check
         orec = O.toks_to_sig(cfg, W, otoks, dt)
     codec.sig_to_toks(sig[:, :1200].cuda())
     _, flat = capture(codec, lambda: codec.sig_to_toks(sig.cuda()), 1 << 26)
-    worst = check_taps(flat, ENC_TAPS, lambda t: et[t].numpy(), 5e-6)
+    worst = check_taps(flat, [t.name for t in LC.taps_of("wavtokenizer", cfg, "encode")], lambda t: et[t].numpy(), 5e-6)
     rec, flat = capture(codec, lambda: codec.toks_to_sig(otoks.cuda()), 1 << 26)
-    worst.update(check_taps(flat, dec_taps(cfg), lambda t: dt[t].numpy(), 1e-5))
+    worst.update(check_taps(flat, [t.name for t in LC.taps_of("wavtokenizer", cfg, "decode")], lambda t: dt[t].numpy(), 1e-5))
     err = rms((rec.cpu() - orec).numpy())
     parity_record.record("wavtokenizer", "full_config_module_taps", worst_rel_err_per_tap=worst, waveform_rms_err=err)
     assert err < 2e-5
