@@ -163,6 +163,8 @@ EXPORTS = {
     "ac_mimi_stream_decode_reset": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
     "ac_mimi_stream_decode_workspace_bytes": (_sz, [_vp, _i, _i]),
     "ac_mimi_stream_decode": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ac_mimi_stream_encode_slots": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "ac_mimi_stream_decode_slots": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "ac_encodec_stream_state_bytes": (_sz, [_vp, _i]),
     "ac_encodec_stream_reset": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
     "ac_encodec_stream_workspace_bytes": (_sz, [_vp, _i, _i]),

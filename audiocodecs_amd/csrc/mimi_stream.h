@@ -7,6 +7,10 @@
 //   mstream_upsample_kernel  the depthwise stride-s transposed conv on [previous input row | chunk]
 // The staging, linear, advance and reset kernels (mstream_stage*_kernel, mstream_cache_tail_kernel, mstream_linear_kernel,
 // mstream_advance_kernel, mstream_reset_kernel; a reset does not touch the rings) are shared with the EnCodec stream: stream_stage.h.
+// A slot push (ac_mimi_stream_*_slots) runs n listed streams of the `cap` the state holds: qkv and out stay dense
+// [n] rows, and only the position and the ring rows go through the slot map (`slot`, stream_stage.h mstream_slot; null = identity,
+// the lockstep push, whose code path is untouched).  A row whose entry is outside [0, cap) is at position 0, reads no ring row -- at
+// position 0 every visible key lies in the push -- and appends nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,7 +56,15 @@ struct MStreamRopeParams {
     const long long* pos;        // [B] absolute position of row 0
     int B, T, A, HD;
     float inv[MSTREAM_MAXHD / 2];  // inv_freq (fp32), as the batch table's
+    const int* slot = nullptr;   // null: row b is stream b.  Else [B] (device): pos[slot[b]] of the `cap` streams the state holds
+    int cap = 0;
 };
+
+// the stream of row b in a slot push (-1: none) and its position (0 for none)
+__device__ __forceinline__ long long mstream_slot_pos(const long long* pos, const int* slot, int b, int cap, int* sb) {
+    *sb = mstream_slot(slot, b, cap);
+    return *sb >= 0 ? pos[*sb] : 0;
+}
 
 // x cos + rotate_half(x) sin ([HF] mimi :582-599), each factor as the batch table computes it: angle = inv[j] * (float)p in fp32,
 // cos / sin rounded once from double; products and sum unfused like attention_kernel's stage_rope.
@@ -67,7 +79,9 @@ __global__ __launch_bounds__(256) void mstream_rope_kernel(const MStreamRopePara
         const int which = (int)(r % 2);
         const long long row = r / 2;                  // b*T + t
         const int b = (int)(row / p.T), t = (int)(row % p.T);
-        const float ang = p.inv[j] * (float)(p.pos[b] + t);
+        int sb;
+        const long long p0 = p.slot ? mstream_slot_pos(p.pos, p.slot, b, p.cap, &sb) : p.pos[b];
+        const float ang = p.inv[j] * (float)(p0 + t);
         const float cv = (float)cos((double)ang), sv = (float)sin((double)ang);
         float* x = p.qkv + row * 3 * p.A + (long long)which * p.A + (long long)hh * p.HD;
         const float lo = x[j], hi = x[j + half];
@@ -84,16 +98,27 @@ struct MStreamAttnParams {
     float* out;                  // [B][T][A]
     int B, T, A, HD, window, R;
     float scaling;
+    const int* slot = nullptr;   // null: row b is stream b.  Else [B] (device): position and ring rows of stream slot[b] of `cap`
+    int cap = 0;
 };
 
 // One wave per (query row, head, stream), keys 64 at a time (one per lane), online softmax in fp32 with exact FMA products.
 // Key j is visible to query i iff j <= i and i - j < window; positions below 0 (before the stream's reset) do not exist.
+// In a slot push every blockIdx.z has its own position: ring phase, window start and number of key blocks are per wave.
 __global__ __launch_bounds__(256) void mstream_attn_kernel(const MStreamAttnParams p) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int hh = blockIdx.y, b = blockIdx.z;
     if (i >= p.T) return;                                 // (whole wave)
-    const long long P0 = p.pos[b], qa = P0 + i;
+    int sb = b;                                           // the stream whose ring this row reads
+    long long P0;
+    if (p.slot) {
+        P0 = mstream_slot_pos(p.pos, p.slot, b, p.cap, &sb);
+        if (sb < 0) sb = 0;                               // (P0 = 0: no key below it, the ring is not read)
+    } else {
+        P0 = p.pos[b];
+    }
+    const long long qa = P0 + i;
     const long long rs = 3LL * p.A;
     const float* qrow = p.qkv + ((long long)b * p.T + i) * rs + (long long)hh * p.HD;
     const float qv = lane < p.HD ? qrow[lane] : 0.f;
@@ -102,7 +127,7 @@ __global__ __launch_bounds__(256) void mstream_attn_kernel(const MStreamAttnPara
     float m = -INFINITY, l = 0.f, acc = 0.f;
     auto key_row = [&](long long j, const float* ring, int which) -> const float* {
         if (j >= P0) return p.qkv + ((long long)b * p.T + (j - P0)) * rs + (long long)which * p.A + (long long)hh * p.HD;
-        return ring + ((long long)b * p.R + (j % p.R)) * p.A + (long long)hh * p.HD;
+        return ring + ((long long)sb * p.R + (j % p.R)) * p.A + (long long)hh * p.HD;
     };
     for (long long jb = j0; jb <= qa; jb += 64) {
         const long long j = jb + lane;
@@ -137,6 +162,8 @@ struct MStreamAppendParams {
     float* rv;
     const long long* pos;
     int B, T, A, R;
+    const int* slot = nullptr;   // null: row b is stream b.  Else [B] (device): position and ring rows of stream slot[b] of `cap`
+    int cap = 0;
 };
 
 // the last min(T, R) rows of the push -> ring slots (position % R)
@@ -148,9 +175,17 @@ __global__ __launch_bounds__(256) void mstream_append_kernel(const MStreamAppend
         const long long r = e / p.A;
         const int t = p.T - keep + (int)(r % keep), b = (int)(r / keep);
         const float* src = p.qkv + ((long long)b * p.T + t) * 3 * p.A + c;
-        long long r_ = (p.pos[b] + t) % p.R;
+        int sb = b;
+        long long p0;
+        if (p.slot) {
+            p0 = mstream_slot_pos(p.pos, p.slot, b, p.cap, &sb);
+            if (sb < 0) continue;                     // (a row of no stream appends nothing)
+        } else {
+            p0 = p.pos[b];
+        }
+        long long r_ = (p0 + t) % p.R;
         if (r_ < 0) r_ += p.R;                        // (a position is never negative once reset; the slot stays in the ring regardless)
-        const long long slot = ((long long)b * p.R + r_) * p.A + c;
+        const long long slot = ((long long)sb * p.R + r_) * p.A + c;
         p.rk[slot] = src[p.A];
         p.rv[slot] = src[2 * p.A];
     }

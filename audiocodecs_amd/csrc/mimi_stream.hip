@@ -11,6 +11,9 @@
 // k = 2 stride it is convtr_fwd's 2-tap row conv, its left zero row replaced by the cached one), each residual block's k3 history
 // and the head conv's.  A decode state has its own layout and magic and is registered separately on the handle.  The transformer's
 // linear layers of a push with few rows go through mstream_linear_kernel (stream_stage.h) instead of the tap-GEMM.
+//
+// Slot pushes (ac_mimi_stream_encode_slots / _decode_slots) run n listed streams of the B a state holds: the same
+// launch sequence on n dense rows, with the conv caches, the positions and the K / V rings addressed through the caller's slot list.
 #include "core.h"
 #include "stream_launch.h"
 #include "mimi_stream.h"
@@ -25,11 +28,13 @@ struct MStreamLayout {
     size_t ring = 0;                           // per transformer layer: keys [B][R][A], then values [B][R][A]
     int R = 0, A = 0;
     size_t total = 0;
+    int B = 0;                                 // streams the state holds
 };
 
 static MStreamLayout mstream_layout(const ac_handle* h, int B) {
     const ac_mimi_config& c = h->mcfg;
     MStreamLayout L;
+    L.B = B;
     size_t off = align_up(sizeof(MStreamHeader), 256);
     auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
     L.pos = take((size_t)B * 8);
@@ -57,6 +62,7 @@ static MStreamLayout mstream_layout(const ac_handle* h, int B) {
 static MStreamLayout mdstream_layout(const ac_handle* h, int B) {
     const ac_mimi_config& c = h->mcfg;
     MStreamLayout L;
+    L.B = B;
     size_t off = align_up(sizeof(MStreamHeader), 256);
     auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
     L.pos = take((size_t)B * 8);
@@ -88,11 +94,12 @@ static unsigned long long mstream_fingerprint(const ac_mimi_config& c) {
     return f;
 }
 
-// [cache | x] -> staged, x's last P rows -> cache (stream_launch.h), on cache `l` of the state
-static int mstream_stage(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, int l, const Act& x, int B, float* staged,
+// [cache | x] -> staged, x's last P rows -> cache (stream_launch.h), on cache `l` of the state.
+// (`slot`, here and below: the slot map of a push that runs B listed streams of the state's Ls.B -- stream_stage.h; null = all, in order)
+static int mstream_stage(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const int* slot, int l, const Act& x, int B, float* staged,
                          size_t cap, bool replicate, bool any_L = false) {
     return stream_stage(h, st, reinterpret_cast<float*>(state + Ls.conv[l]), reinterpret_cast<const int*>(state + Ls.fresh), Ls.conv_P[l], Ls.conv_C[l], l, x, B,
-                        staged, cap, replicate ? STAGE_REPLICATE : STAGE_ZERO, any_L);
+                        staged, cap, replicate ? STAGE_REPLICATE : STAGE_ZERO, any_L, slot, Ls.B);
 }
 
 struct MStreamScratch {   // transformer scratch (as mimi_path.hip's TfScratch)
@@ -148,14 +155,15 @@ static int mstream_linear(ac_handle* h, hipStream_t st, const PackedGemm& g, con
 }
 
 // x [B*T][H] in place, as transformer_fwd, with the attention of mstream_attn_kernel.  `skinny`: the linear layers through
-// mstream_linear (the decode stream's choice; the encode stream passes false and keeps the tap-GEMM route bit for bit)
-static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const std::vector<MimiTfLayer>& layers, bool skinny,
-                               float* x, int B, int T, const MStreamScratch& s) {
+// mstream_linear (the decode stream's choice; the encode stream passes false and keeps the tap-GEMM route bit for bit).
+// B is the dense row count of the push: every activation is [B][T]; only the positions and the rings ([Ls.B] streams) go through `slot`.
+static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const int* slot, const std::vector<MimiTfLayer>& layers,
+                               bool skinny, float* x, int B, int T, const MStreamScratch& s) {
     const ac_mimi_config& c = h->mcfg;
     const int H = c.hidden_size, A = Ls.A, I = c.intermediate_size, R = Ls.R;
     const long long rows = (long long)B * T;
     const long long* pos = reinterpret_cast<const long long*>(state + Ls.pos);
-    const size_t ring_bytes = align_up((size_t)B * R * A * 4, 256);
+    const size_t ring_bytes = align_up((size_t)Ls.B * R * A * 4, 256);
     MStreamRopeParams rp{};
     rp.qkv = s.qkv;
     rp.pos = pos;
@@ -164,6 +172,8 @@ static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const 
     rp.A = A;
     rp.HD = c.head_dim;
     rope_inv(h, rp.inv);
+    rp.slot = slot;
+    rp.cap = Ls.B;
     for (size_t l = 0; l < layers.size(); ++l) {
         const MimiTfLayer& L = layers[l];
         float* rk = reinterpret_cast<float*>(state + Ls.ring + (2 * l) * ring_bytes);
@@ -181,14 +191,14 @@ static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const 
             HIPCHK(h, hipGetLastError());
         }
         {
-            MStreamAttnParams ap{s.qkv, rk, rv, pos, s.att, B, T, A, c.head_dim, c.sliding_window, R, 1.0f / std::sqrt((float)c.head_dim)};
+            MStreamAttnParams ap{s.qkv, rk, rv, pos, s.att, B, T, A, c.head_dim, c.sliding_window, R, 1.0f / std::sqrt((float)c.head_dim), slot, Ls.B};
             const double keys = std::min<double>(c.sliding_window, T + R);
             ProfScope ps(h, st, "mstream_attn_kernel", 4.0 * rows * A * keys, 8.0 * rows * A * keys);
             hipLaunchKernelGGL(mstream_attn_kernel, dim3(cdiv(T, 4), c.num_attention_heads, B), dim3(256), 0, st, ap);
             HIPCHK(h, hipGetLastError());
         }
         if (R > 0) {   // after the attention: with T >= R the new rows overwrite slots earlier queries of this push still read
-            MStreamAppendParams pp{s.qkv, rk, rv, pos, B, T, A, R};
+            MStreamAppendParams pp{s.qkv, rk, rv, pos, B, T, A, R, slot, Ls.B};
             const long long n = (long long)B * std::min(T, R) * A;
             ProfScope ps(h, st, "mstream_append_kernel", 0.0, 16.0 * n);
             hipLaunchKernelGGL(mstream_append_kernel, dim3(grid_for(n)), dim3(256), 0, st, pp);
@@ -217,7 +227,7 @@ static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const 
 }
 
 // one push: sig [B][F*hop] -> feats [B][F][H]; the stream state advances by F frames
-static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const float* sig, int B, int F, float* feats,
+static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const int* slot, const float* sig, int B, int F, float* feats,
                            WsPtrs& ws, size_t cap) {
     const ac_mimi_config& c = h->mcfg;
     const MimiPlan& m = h->mimi;
@@ -225,7 +235,7 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
     int l = 0, rc;
     Act2 x, y;
     float* stg = ws.take();
-    if ((rc = mstream_stage(h, st, state, Ls, l, Act{sig, (long long)T, 1, T, 1}, B, stg, cap, false))) return rc;
+    if ((rc = mstream_stage(h, st, state, Ls, slot, l, Act{sig, (long long)T, 1, T, 1}, B, stg, cap, false))) return rc;
     if ((rc = mstream_conv(h, st, m.enc_stem, staged_act(stg, B, T + Ls.conv_P[l], 1), c.kernel_size, 1, T, Out{ws.take(), ws.take()}, B, &x))) return rc;
     ws.give(stg);
     ++l;
@@ -235,7 +245,7 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
         const int L = x.raw.L, ch = rb.C;
         // residual block: x + conv_k1(ELU(conv_k3(ELU(x)))), the k3 conv on [history | ELU(x)]
         stg = ws.take();
-        if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false))) return rc;
+        if ((rc = mstream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, false))) return rc;
         ws.give(x.elu.p);
         float* hb = ws.take();
         Act2 hv;
@@ -252,7 +262,7 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
         x = y;
         // down-sampler (k = 2 * ratio, stride ratio) on [history | ELU(x)]
         stg = ws.take();
-        if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false))) return rc;
+        if ((rc = mstream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, false))) return rc;
         ws.give(x);
         const bool last = i == c.num_ratios - 1;     // the last one feeds ELU -> final conv only
         if ((rc = mstream_conv(h, st, m.enc_down[i], staged_act(stg, B, L + Ls.conv_P[l], ch), 2 * ratio, ratio, L / ratio,
@@ -263,31 +273,31 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
     }
     const int T25 = x.elu.L;
     stg = ws.take();
-    if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false))) return rc;
+    if ((rc = mstream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, false))) return rc;
     ws.give(x);
     float* stream = ws.take();
     if ((rc = mstream_conv(h, st, m.enc_final, staged_act(stg, B, T25 + Ls.conv_P[l], m.D), c.last_kernel_size, 1, T25, Out{stream, nullptr}, B, nullptr))) return rc;
     ws.give(stg);
     ++l;
     MStreamScratch s{ws.take(), ws.take(), ws.take(), ws.take()};
-    if ((rc = mstream_transformer(h, st, state, Ls, m.enc_tf, false, stream, B, T25, s))) return rc;
+    if ((rc = mstream_transformer(h, st, state, Ls, slot, m.enc_tf, false, stream, B, T25, s))) return rc;
     ws.give(s.ln); ws.give(s.qkv); ws.give(s.att); ws.give(s.hid);
     stg = ws.take();
     const int H = c.hidden_size;
-    if ((rc = mstream_stage(h, st, state, Ls, l, Act{stream, (long long)T25 * H, H, T25, H}, B, stg, cap, true))) return rc;
+    if ((rc = mstream_stage(h, st, state, Ls, slot, l, Act{stream, (long long)T25 * H, H, T25, H}, B, stg, cap, true))) return rc;
     ws.give(stream);
     if ((rc = mstream_conv(h, st, m.down, staged_act(stg, B, T25 + Ls.conv_P[l], H), 2 * c.resample_stride, c.resample_stride, F,
                            Out{feats, nullptr}, B, nullptr)))
         return rc;
     ws.give(stg);
     hipLaunchKernelGGL(mstream_advance_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
-                       reinterpret_cast<int*>(state + Ls.fresh), B, T25, static_cast<const int*>(nullptr), B);   // (no slot map: stream_stage.h)
+                       reinterpret_cast<int*>(state + Ls.fresh), B, T25, slot, Ls.B);
     HIPCHK(h, hipGetLastError());
     return AC_OK;
 }
 
 // one push: toks [B][F][K] -> sig [B][F*hop]; the decode state advances by F frames (mimi_decoder_fwd on [history | chunk])
-static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const long long* toks, int B, int F, int K, float* sig,
+static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const int* slot, const long long* toks, int B, int F, int K, float* sig,
                            WsPtrs& ws, size_t cap, bool skinny) {
     const ac_mimi_config& c = h->mcfg;
     const MimiPlan& m = h->mimi;
@@ -299,7 +309,7 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
     ws.give(qsum);
     // up-sampler: depthwise transposed conv (k = 2 stride) on [previous input row | chunk]
     float* stg = ws.take();
-    if ((rc = mstream_stage(h, st, state, Ls, l, Act{qf, (long long)F * H, H, F, H}, B, stg, cap, false, true))) return rc;
+    if ((rc = mstream_stage(h, st, state, Ls, slot, l, Act{qf, (long long)F * H, H, F, H}, B, stg, cap, false, true))) return rc;
     ws.give(qf);
     ++l;
     float* stream = ws.take();
@@ -313,12 +323,12 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
     }
     ws.give(stg);
     MStreamScratch s{ws.take(), ws.take(), ws.take(), ws.take()};
-    if ((rc = mstream_transformer(h, st, state, Ls, m.dec_tf, skinny, stream, B, T25, s))) return rc;
+    if ((rc = mstream_transformer(h, st, state, Ls, slot, m.dec_tf, skinny, stream, B, T25, s))) return rc;
     ws.give(s.ln); ws.give(s.qkv); ws.give(s.att); ws.give(s.hid);
     // first conv (k7) on [history | chunk]: a one-frame push brings fewer rows than the history holds
     Act2 x, y;
     stg = ws.take();
-    if ((rc = mstream_stage(h, st, state, Ls, l, Act{stream, (long long)T25 * H, H, T25, H}, B, stg, cap, false, true))) return rc;
+    if ((rc = mstream_stage(h, st, state, Ls, slot, l, Act{stream, (long long)T25 * H, H, T25, H}, B, stg, cap, false, true))) return rc;
     ws.give(stream);
     if ((rc = mstream_conv(h, st, m.dec_first, staged_act(stg, B, T25 + Ls.conv_P[l], H), c.kernel_size, 1, T25, Out{nullptr, ws.take()}, B, &x))) return rc;
     ws.give(stg);
@@ -327,7 +337,7 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
         const int ratio = c.upsampling_ratios[i], cin = m.dec_up[i].Ktot / 2, cup = m.dec_up[i].N / ratio, L = x.elu.L;
         // transposed conv (k = 2 ratio): output row m = [x[m-1] | x[m]] Wp (convtr_fwd), x[-1] from the cache
         stg = ws.take();
-        if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false, true))) return rc;
+        if ((rc = mstream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, false, true))) return rc;
         ws.give(x);
         if ((rc = mstream_conv(h, st, m.dec_up[i], staged_act(stg, B, L + Ls.conv_P[l], cin), 2, 1, L, Out{ws.take(), ws.take()}, B, &y))) return rc;
         ws.give(stg);
@@ -338,7 +348,7 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
         // residual block: x + conv_k1(ELU(conv_k3(ELU(x)))), the k3 conv on [history | ELU(x)]
         const ResBlockPlan& rb = m.dec_rb[i];
         stg = ws.take();
-        if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false, true))) return rc;
+        if ((rc = mstream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, false, true))) return rc;
         ws.give(x.elu.p);
         float* hb = ws.take();
         Act2 hv;
@@ -357,12 +367,12 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
     }
     const int Ts = x.elu.L, Fh = c.num_filters;
     stg = ws.take();
-    if ((rc = mstream_stage(h, st, state, Ls, l, x.elu, B, stg, cap, false, true))) return rc;
+    if ((rc = mstream_stage(h, st, state, Ls, slot, l, x.elu, B, stg, cap, false, true))) return rc;
     ws.give(x);
     if ((rc = mstream_conv(h, st, m.dec_head, staged_act(stg, B, Ts + Ls.conv_P[l], Fh), c.last_kernel_size, 1, Ts, Out{sig, nullptr}, B, nullptr))) return rc;
     ws.give(stg);
     hipLaunchKernelGGL(mstream_advance_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, st, reinterpret_cast<long long*>(state + Ls.pos),
-                       reinterpret_cast<int*>(state + Ls.fresh), B, T25, static_cast<const int*>(nullptr), B);   // (no slot map: stream_stage.h)
+                       reinterpret_cast<int*>(state + Ls.fresh), B, T25, slot, Ls.B);
     HIPCHK(h, hipGetLastError());
     return AC_OK;
 }
@@ -387,6 +397,83 @@ static int mstream_check(ac_handle* h, int B, bool dec = false) {
     if (B < 1) return fail(h, AC_EINVAL, "ac_mimi_stream: B=%d", B);
     if (h->mcfg.head_dim > MSTREAM_MAXHD) return fail(h, AC_EINVAL, "ac_mimi_stream: head_dim %d unsupported", h->mcfg.head_dim);
     return AC_OK;
+}
+
+// a slot list (host memory): 1 <= n <= B entries in [0, B), none twice
+static int mstream_slots_check(ac_handle* h, const int* slots, int n, int B, const char* who) {
+    if (n < 1 || n > B) return fail(h, AC_EINVAL, "%s: n=%d slots of a state of %d", who, n, B);
+    std::vector<uint8_t> seen((size_t)B, 0);
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= B) return fail(h, AC_EINVAL, "%s: slot %d outside [0, %d)", who, slots[i], B);
+        if (seen[slots[i]]) return fail(h, AC_EINVAL, "%s: slot %d listed twice", who, slots[i]);
+        seen[slots[i]] = 1;
+    }
+    return AC_OK;
+}
+
+// a slot call's own arguments (the rest is the push's); a null handle falls through to the push's check
+static int mslots_args(ac_handle* h, const int* slots_host, const int* slots_dev, const char* who) {
+    if (h && (!slots_host || !slots_dev)) return fail(h, AC_EINVAL, "%s: the slot list is null", who);
+    return AC_OK;
+}
+
+// One push of n streams of a state of B: all of them in order (a lockstep push: slots_host = slots_dev = null, n = B) or the listed
+// ones.  Every buffer, scale and launch shape is that of a dense push of n streams; `slots_dev` only redirects the addresses into the
+// state.  Mimi pads with zeros: a fresh stream takes any F >= 1, and the host keeps no per-slot record.
+static int mstream_encode(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                          const float* sig_dev, int F, int K, int64_t* toks_dev, void* ws, size_t ws_bytes, void* stream, const char* who) {
+    int rc = mstream_check(h, B);
+    if (rc) return rc;
+    if (!state_dev || !sig_dev || !toks_dev || F < 1) return fail(h, AC_EINVAL, "%s: bad argument (F=%d)", who, F);
+    if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "%s: K=%d outside [1, %d]", who, K, h->mcfg.num_quantizers);
+    auto it = h->mimi_streams.find(state_dev);
+    if (it == h->mimi_streams.end())
+        return fail(h, AC_EINVAL, "%s: the state was never reset on this handle%s", who, h->mimi_dstreams.count(state_dev) ? " as an encode state (it is a decode state)" : "");
+    if (it->second != B) return fail(h, AC_EINVAL, "%s: the state holds %d streams, B=%d", who, it->second, B);
+    const MStreamLayout Ls = mstream_layout(h, B);
+    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "%s: state of %zu bytes, %zu needed", who, state_bytes, Ls.total);
+    if ((long long)F * h->hop > 0x7fffffffLL / 64) return fail(h, AC_EINVAL, "%s: F=%d frames per push is too many", who, F);
+    if (slots_host && (rc = mstream_slots_check(h, slots_host, n, B, who))) return rc;
+    const Workspace w = mstream_plan_ws(h, n, F);
+    WsPtrs p;
+    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = amax_begin(h, st, n))) return rc;
+    const ac_mimi_config& c = h->mcfg;
+    float* feats = p.act[NACT - 1];   // the push never has more than 5 buffers live
+    p.used[NACT - 1] = true;
+    rc = mstream_encoder(h, st, static_cast<char*>(state_dev), Ls, slots_dev, sig_dev, n, F, feats, p, w.act_floats);
+    if (rc) return rc;
+    float* proj = p.take();
+    rc = mimi_linear(h, st, h->mimi.in_proj, feats, (long long)n * F, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
+    if (rc) return rc;
+    return mimi_rvq_encode(h, st, proj, n * F, K, reinterpret_cast<long long*>(toks_dev));
+}
+
+static int mstream_decode(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                          const int64_t* toks_dev, int F, int K, float* sig_dev, void* ws, size_t ws_bytes, void* stream, const char* who) {
+    int rc = mstream_check(h, B, true);
+    if (rc) return rc;
+    if (!state_dev || !sig_dev || !toks_dev || F < 1) return fail(h, AC_EINVAL, "%s: bad argument (F=%d)", who, F);
+    if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "%s: K=%d outside [1, %d]", who, K, h->mcfg.num_quantizers);
+    auto it = h->mimi_dstreams.find(state_dev);
+    if (it == h->mimi_dstreams.end())
+        return fail(h, AC_EINVAL, "%s: the state was never reset as a decode state on this handle%s", who,
+                    h->mimi_streams.count(state_dev) ? " (it is an encode state)" : "");
+    if (it->second != B) return fail(h, AC_EINVAL, "%s: the state holds %d streams, B=%d", who, it->second, B);
+    const MStreamLayout Ls = mdstream_layout(h, B);
+    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "%s: state of %zu bytes, %zu needed", who, state_bytes, Ls.total);
+    if ((long long)F * h->hop > 0x7fffffffLL / 64) return fail(h, AC_EINVAL, "%s: F=%d frames per push is too many", who, F);
+    if (slots_host && (rc = mstream_slots_check(h, slots_host, n, B, who))) return rc;
+    const Workspace w = mdstream_plan_ws(h, n, F);
+    WsPtrs p;
+    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = amax_begin(h, st, n))) return rc;
+    const long long rows = (long long)n * F * h->mcfg.resample_stride;      // rows of one linear-layer launch (dense: the listed streams)
+    const int sw = h->dev.mstream_skinny;
+    const bool skinny = sw > 0 || (sw < 0 && rows <= MSTREAM_SKINNY_AUTO_ROWS);
+    return mstream_decoder(h, st, static_cast<char*>(state_dev), Ls, slots_dev, reinterpret_cast<const long long*>(toks_dev), n, F, K, sig_dev, p, w.act_floats, skinny);
 }
 
 }  // namespace acimpl
@@ -427,31 +514,14 @@ int ac_mimi_stream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int 
 
 int ac_mimi_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, const float* sig_dev, int B, int F, int K, int64_t* toks_dev,
                           void* ws, size_t ws_bytes, void* stream) {
-    int rc = mstream_check(h, B);
-    if (rc) return rc;
-    if (!state_dev || !sig_dev || !toks_dev || F < 1) return fail(h, AC_EINVAL, "ac_mimi_stream_encode: bad argument (F=%d)", F);
-    if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "ac_mimi_stream_encode: K=%d outside [1, %d]", K, h->mcfg.num_quantizers);
-    auto it = h->mimi_streams.find(state_dev);
-    if (it == h->mimi_streams.end())
-        return fail(h, AC_EINVAL, "ac_mimi_stream_encode: the state was never reset on this handle%s", h->mimi_dstreams.count(state_dev) ? " as an encode state (it is a decode state)" : "");
-    if (it->second != B) return fail(h, AC_EINVAL, "ac_mimi_stream_encode: the state holds %d streams, B=%d", it->second, B);
-    const MStreamLayout Ls = mstream_layout(h, B);
-    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "ac_mimi_stream_encode: state of %zu bytes, %zu needed", state_bytes, Ls.total);
-    if ((long long)F * h->hop > 0x7fffffffLL / 64) return fail(h, AC_EINVAL, "ac_mimi_stream_encode: F=%d frames per push is too many", F);
-    const Workspace w = mstream_plan_ws(h, B, F);
-    WsPtrs p;
-    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = amax_begin(h, st, B))) return rc;
-    const ac_mimi_config& c = h->mcfg;
-    float* feats = p.act[NACT - 1];   // the push never has more than 5 buffers live
-    p.used[NACT - 1] = true;
-    rc = mstream_encoder(h, st, static_cast<char*>(state_dev), Ls, sig_dev, B, F, feats, p, w.act_floats);
-    if (rc) return rc;
-    float* proj = p.take();
-    rc = mimi_linear(h, st, h->mimi.in_proj, feats, (long long)B * F, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
-    if (rc) return rc;
-    return mimi_rvq_encode(h, st, proj, B * F, K, reinterpret_cast<long long*>(toks_dev));
+    return mstream_encode(h, state_dev, state_bytes, B, nullptr, nullptr, B, sig_dev, F, K, toks_dev, ws, ws_bytes, stream, "ac_mimi_stream_encode");
+}
+
+int ac_mimi_stream_encode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                                const float* sig_dev, int F, int K, int64_t* toks_dev, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "ac_mimi_stream_encode_slots";
+    const int rc = mslots_args(h, slots_host, slots_dev, who);
+    return rc ? rc : mstream_encode(h, state_dev, state_bytes, B, slots_host, slots_dev, n, sig_dev, F, K, toks_dev, ws, ws_bytes, stream, who);
 }
 
 size_t ac_mimi_stream_decode_state_bytes(const ac_handle* h, int B) {
@@ -486,27 +556,14 @@ int ac_mimi_stream_decode_reset(ac_handle* h, void* state_dev, size_t state_byte
 
 int ac_mimi_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K, float* sig_dev,
                           void* ws, size_t ws_bytes, void* stream) {
-    int rc = mstream_check(h, B, true);
-    if (rc) return rc;
-    if (!state_dev || !sig_dev || !toks_dev || F < 1) return fail(h, AC_EINVAL, "ac_mimi_stream_decode: bad argument (F=%d)", F);
-    if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "ac_mimi_stream_decode: K=%d outside [1, %d]", K, h->mcfg.num_quantizers);
-    auto it = h->mimi_dstreams.find(state_dev);
-    if (it == h->mimi_dstreams.end())
-        return fail(h, AC_EINVAL, "ac_mimi_stream_decode: the state was never reset as a decode state on this handle%s",
-                    h->mimi_streams.count(state_dev) ? " (it is an encode state)" : "");
-    if (it->second != B) return fail(h, AC_EINVAL, "ac_mimi_stream_decode: the state holds %d streams, B=%d", it->second, B);
-    const MStreamLayout Ls = mdstream_layout(h, B);
-    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "ac_mimi_stream_decode: state of %zu bytes, %zu needed", state_bytes, Ls.total);
-    if ((long long)F * h->hop > 0x7fffffffLL / 64) return fail(h, AC_EINVAL, "ac_mimi_stream_decode: F=%d frames per push is too many", F);
-    const Workspace w = mdstream_plan_ws(h, B, F);
-    WsPtrs p;
-    if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = amax_begin(h, st, B))) return rc;
-    const long long rows = (long long)B * F * h->mcfg.resample_stride;      // rows of one linear-layer launch
-    const int sw = h->dev.mstream_skinny;
-    const bool skinny = sw > 0 || (sw < 0 && rows <= MSTREAM_SKINNY_AUTO_ROWS);
-    return mstream_decoder(h, st, static_cast<char*>(state_dev), Ls, reinterpret_cast<const long long*>(toks_dev), B, F, K, sig_dev, p, w.act_floats, skinny);
+    return mstream_decode(h, state_dev, state_bytes, B, nullptr, nullptr, B, toks_dev, F, K, sig_dev, ws, ws_bytes, stream, "ac_mimi_stream_decode");
+}
+
+int ac_mimi_stream_decode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
+                                const int64_t* toks_dev, int F, int K, float* sig_dev, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "ac_mimi_stream_decode_slots";
+    const int rc = mslots_args(h, slots_host, slots_dev, who);
+    return rc ? rc : mstream_decode(h, state_dev, state_bytes, B, slots_host, slots_dev, n, toks_dev, F, K, sig_dev, ws, ws_bytes, stream, who);
 }
 
 }  // extern "C"

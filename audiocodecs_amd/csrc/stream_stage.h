@@ -7,7 +7,7 @@
 //   mstream_reset_kernel   header + (masked) position = 0, fresh = 1
 // A push may serve a SUBSET of the state's streams: its activations are dense ([n] rows), and only the addresses into the stream state
 // (cache, fresh, position) go through a slot map -- `slot` [n], row b of the push belongs to stream slot[b]; null = identity
-// (mstream_slot).  Mimi passes null everywhere; EnCodec's slot pushes pass the caller's list (encodec_stream.hip).
+// (mstream_slot).  Lockstep pushes pass null; the slot pushes of both codecs pass the caller's list (encodec_stream.hip, mimi_stream.hip).
 // Every kernel here is a template (the dummy parameter of those that need none): two translation units include this header, and the
 // library keeps one definition of every non-template kernel (core.h).
 #pragma once

@@ -18,8 +18,9 @@ from .codec import Codec
 from .config import MIMI_24KHZ, MimiConfig
 from .encodec import _ptr, _stream
 from .resample import ResampleStream
+from .sessions import plan_push
 
-__all__ = ["Mimi", "MimiEncodeStream", "MimiDecodeStream"]
+__all__ = ["Mimi", "MimiEncodeStream", "MimiDecodeStream", "MimiEncodeSessions", "MimiDecodeSessions"]
 
 
 class _NativeMimi:
@@ -272,6 +273,32 @@ class Mimi(Codec):
         self._check_num_codebooks()
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         return MimiDecodeStream(self, self._native_for(torch.empty(0, device=dev)), batch_size, bool(resample))
+
+    # ---- session pools ---------------------------------------------------------------------------
+    def _sessions_checks(self, what: str, capacity, device) -> _NativeMimi:
+        need, lacks = ("encoder", "decode") if what.startswith("encode") else ("decoder", "encode")
+        if self.mode == lacks:
+            raise ValueError(f"{what} needs the {need}: this Mimi was built with mode=\"{lacks}\"")
+        if self.sample_rate != self.config.sampling_rate:
+            raise ValueError(
+                f"{what} runs at the codec's own rate ({self.config.sampling_rate} Hz): streaming resampling from or to "
+                f"sample_rate={self.sample_rate} is not available per slot"
+            )
+        if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
+            raise ValueError(f"`capacity` ({capacity!r}) must be a positive int")
+        self._check_num_codebooks()
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return self._native_for(torch.empty(0, device=dev))
+
+    def encode_sessions(self, capacity: int, device=None) -> "MimiEncodeSessions":
+        """A pool of up to `capacity` independent encode sessions on one stream state: sessions `open` and `close` at any time and
+        `push(slots, sig)` serves any subset of them, each at its own position and with the bits of a lone `encode_stream(1)`
+        (DESIGN.md section 8g).  Runs at the codec's own rate only."""
+        return MimiEncodeSessions(self, self._sessions_checks("encode_sessions", capacity, device), capacity)
+
+    def decode_sessions(self, capacity: int, device=None) -> "MimiDecodeSessions":
+        """The decode side of `encode_sessions`: `push(slots, toks)` returns every listed session's samples."""
+        return MimiDecodeSessions(self, self._sessions_checks("decode_sessions", capacity, device), capacity)
 
     # ---- measurement hook used by bench.py ------------------------------------------------------
     def profile_kernels(self, fn):
@@ -536,3 +563,194 @@ class MimiDecodeStream:
                                                      _ptr(self._ws), self._ws.numel(), _stream()), "ac_mimi_stream_decode")
         self._frames = [f + F for f in self._frames]
         return sig
+
+
+class _MimiSessions:
+    """A pool of independent sessions on one Mimi stream state (include/audiocodecs_amd.h ac_mimi_stream_*_slots).
+
+    The state holds `capacity` slots.  `open` hands out the lowest free one and restarts it alone (the masked reset of the lockstep
+    stream); `push(slots, x)` runs any subset, row i of `x` belonging to `slots[i]`.  Partial frames wait per slot; Mimi pads with
+    zeros, so a fresh slot runs its first whole frame at once (no warm-up hold, unlike the EnCodec pools).  The rows of a push that
+    run the same number of frames share one native call, the groups going out in ascending F (sessions.plan_push, warmup = 1); a
+    slot's bits are those of a lone stream fed the same pieces, whichever slot it sits in and whatever the others do."""
+
+    MAX_POSITIONS = 1 << 24     # transformer positions per session (fp32 RoPE angle)
+    _unit = 1          # units per frame in what a slot holds back: samples on the encode side, token frames on the decode side
+
+    def __init__(self, codec: Mimi, nat: _NativeMimi, capacity: int, kind: str):
+        self.codec = codec
+        self._nat = nat
+        self.capacity = capacity
+        self.num_codebooks = codec.num_codebooks
+        self.hop = codec.config.hop_length
+        self._stride = codec.config.resample_stride      # transformer positions per frame
+        self.device = nat.device
+        L = nat.lib
+        self._fns = {
+            "encode": (L.ac_mimi_stream_state_bytes, L.ac_mimi_stream_reset, L.ac_mimi_stream_workspace_bytes, L.ac_mimi_stream_encode_slots),
+            "decode": (L.ac_mimi_stream_decode_state_bytes, L.ac_mimi_stream_decode_reset, L.ac_mimi_stream_decode_workspace_bytes,
+                       L.ac_mimi_stream_decode_slots),
+        }[kind]
+        self._kind = kind
+        nbytes = self._fns[0](nat.h, capacity)
+        if nbytes == 0:
+            raise _native.NativeError(f"ac_mimi_stream_{'decode_' if kind == 'decode' else ''}state_bytes returned 0")
+        self._state_buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self._state_buf.data_ptr()) % 256
+        self._state = self._state_buf[off:off + nbytes]
+        self._ws = None
+        self._is_open = [False] * capacity
+        self._ran = [0] * capacity              # frames run since the slot was opened
+        self._held = [self._empty()] * capacity  # what waits per slot: [m] samples (decode: nothing ever waits)
+        self._reset(None)                       # the one whole reset: the header, and the handle's record of the address
+
+    def _reset(self, mask) -> None:
+        nat = self._nat
+        with torch.cuda.device(self.device):
+            _native.check(self._fns[1](nat.h, _ptr(self._state), self._state.numel(), self.capacity, _ptr(mask), _stream()), nat.h,
+                          f"ac_mimi_stream_{'decode_' if self._kind == 'decode' else ''}reset")
+
+    # -- the slots -----------------------------------------------------------------------------------------------------------------
+    @property
+    def active(self):
+        """The open slots, ascending."""
+        return [s for s in range(self.capacity) if self._is_open[s]]
+
+    def _slot(self, slot) -> int:
+        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.capacity:
+            raise ValueError(f"slot {slot!r} is outside [0, {self.capacity})")
+        if not self._is_open[slot]:
+            raise ValueError(f"slot {slot} is not open")
+        return slot
+
+    def pending(self, slot: int) -> int:
+        """Units of `slot` that have not run: samples on the encode side, token frames (always 0) on the decode side."""
+        return int(self._held[self._slot(slot)].shape[0])
+
+    def frames(self, slot: int) -> int:
+        """Frames `slot` has run since it was opened."""
+        return self._ran[self._slot(slot)]
+
+    @torch.no_grad()
+    def open(self) -> int:
+        """Take the lowest free slot and restart it alone (the others keep running); ValueError when the pool is full."""
+        free = [s for s in range(self.capacity) if not self._is_open[s]]
+        if not free:
+            raise ValueError(f"the pool is full: all {self.capacity} slots are open")
+        slot = free[0]
+        mask = torch.zeros(self.capacity, dtype=torch.uint8)
+        mask[slot] = 1
+        self._reset(mask.to(self.device))
+        self._is_open[slot] = True
+        self._ran[slot] = 0
+        self._held[slot] = self._empty()
+        return slot
+
+    def close(self, slot: int) -> None:
+        """Free `slot`, dropping the partial frame it holds."""
+        slot = self._slot(slot)
+        self._is_open[slot] = False
+        self._held[slot] = self._empty()
+
+    # -- a push --------------------------------------------------------------------------------------------------------------------
+    def _check_push(self, slots, x):
+        try:
+            slots = list(slots)
+        except TypeError:
+            raise ValueError(f"push expects a sequence of slots, got {type(slots)}")
+        for s in slots:
+            self._slot(s)
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"push: a slot is listed twice in {slots}")
+        self._check_rows(len(slots), x)
+        return slots
+
+    def _run(self, slots, src: torch.Tensor, F: int, dst: torch.Tensor) -> None:
+        nat, n = self._nat, len(slots)
+        with torch.cuda.device(self.device):
+            need = self._fns[2](nat.h, n, F)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            host = (C.c_int * n)(*slots)
+            dev = torch.tensor(slots, dtype=torch.int32, device=self.device)
+            _native.check(self._fns[3](nat.h, _ptr(self._state), self._state.numel(), self.capacity, host, _ptr(dev), n, _ptr(src), F,
+                                       self.num_codebooks, _ptr(dst), _ptr(self._ws), self._ws.numel(), _stream()), nat.h,
+                          f"ac_mimi_stream_{self._kind}_slots")
+        for s in slots:
+            self._ran[s] += F
+
+    @torch.no_grad()
+    def push(self, slots, x: torch.Tensor):
+        """Feed row i of `x` to `slots[i]` (n distinct open slots); returns n tensors, what each slot releases (possibly nothing)."""
+        slots = self._check_push(slots, x)
+        unit = self._unit
+        plan = plan_push([int(self._held[s].shape[0]) for s in slots], [self._ran[s] for s in slots], [int(x.shape[1])] * len(slots), unit, 1)
+        for F, rows in plan:
+            for i in rows:
+                if self._stride * (self._ran[slots[i]] + F) > self.MAX_POSITIONS:
+                    raise ValueError(f"slot {slots[i]} would pass {self.MAX_POSITIONS} transformer positions: close it and open a new session")
+        whole = [torch.cat([self._held[s], x[i]], 0) if self._held[s].shape[0] else x[i] for i, s in enumerate(slots)]
+        out = [self._nothing() for _ in slots]
+        for F, rows in plan:
+            src = torch.stack([whole[i][: F * unit] for i in rows], 0).contiguous()
+            dst = self._result(len(rows), F)
+            self._run([slots[i] for i in rows], src, F, dst)
+            for j, i in enumerate(rows):
+                out[i] = dst[j]
+                whole[i] = whole[i][F * unit:]
+        for i, s in enumerate(slots):
+            self._held[s] = whole[i].clone()
+        return out
+
+
+class MimiEncodeSessions(_MimiSessions):
+    """A pool of encode sessions (Mimi.encode_sessions).  `push(slots, sig)`: `sig` is [n, L] fp32 on the codec's device, any
+    L >= 0; returns n int64 tensors [f_i, K], the tokens of the frames each slot completes."""
+
+    def __init__(self, codec: Mimi, nat: _NativeMimi, capacity: int):
+        self._unit = codec.config.hop_length
+        super().__init__(codec, nat, capacity, "encode")
+
+    def _empty(self):
+        return torch.empty(0, dtype=torch.float32, device=self.device)
+
+    def _nothing(self):
+        return torch.empty(0, self.num_codebooks, dtype=torch.int64, device=self.device)
+
+    def _result(self, n, F):
+        return torch.empty(n, F, self.num_codebooks, dtype=torch.int64, device=self.device)
+
+    def _check_rows(self, n, sig):
+        if not isinstance(sig, torch.Tensor) or sig.dim() != 2 or sig.shape[0] != n:
+            raise ValueError(f"push expects a [{n}, L] tensor for {n} slots, got {tuple(sig.shape) if isinstance(sig, torch.Tensor) else type(sig)}")
+        if sig.dtype != torch.float32:
+            raise ValueError(f"push expects float32 samples, got {sig.dtype}")
+        if sig.device != self.device:
+            raise ValueError(f"push expects samples on {self.device}, got {sig.device}")
+
+
+class MimiDecodeSessions(_MimiSessions):
+    """A pool of decode sessions (Mimi.decode_sessions).  `push(slots, toks)`: `toks` is [n, F, K] int64 on the codec's device,
+    K = the codec's `num_codebooks`, any F >= 0; returns n fp32 tensors [F * hop], the samples of each slot's frames."""
+
+    def __init__(self, codec: Mimi, nat: _NativeMimi, capacity: int):
+        super().__init__(codec, nat, capacity, "decode")
+
+    def _empty(self):
+        return torch.empty(0, self.num_codebooks, dtype=torch.int64, device=self.device)
+
+    def _nothing(self):
+        return torch.empty(0, dtype=torch.float32, device=self.device)
+
+    def _result(self, n, F):
+        return torch.empty(n, F * self.hop, dtype=torch.float32, device=self.device)
+
+    def _check_rows(self, n, toks):
+        K = self.num_codebooks
+        if not isinstance(toks, torch.Tensor) or toks.dim() != 3 or toks.shape[0] != n or toks.shape[2] != K:
+            raise ValueError(f"push expects a [{n}, F, {K}] tensor for {n} slots, got {tuple(toks.shape) if isinstance(toks, torch.Tensor) else type(toks)}")
+        if toks.dtype != torch.int64:
+            raise ValueError(f"push expects int64 tokens, got {toks.dtype}")
+        if toks.device != self.device:
+            raise ValueError(f"push expects tokens on {self.device}, got {toks.device}")

@@ -1,4 +1,5 @@
-"""The grouping rule of a session pool (Encodec.encode_sessions / decode_sessions), as a pure function.
+"""The grouping rule of a session pool (Encodec.encode_sessions / decode_sessions; Mimi.encode_sessions /
+decode_sessions, section 8g, with warmup = 1: Mimi pads with zeros and holds nothing back), as a pure function.
 
 A pool serves sessions that begin and end at different times on one stream state.  Every slot follows the rule a whole lockstep
 stream follows (encodec.py `EncodecEncodeStream._take` / `EncodecDecodeStream._decode`): units that do not fill a frame wait, and a

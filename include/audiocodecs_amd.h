@@ -325,6 +325,33 @@ size_t ac_mimi_stream_decode_workspace_bytes(const ac_handle* h, int B, int F);
 int ac_mimi_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K,
                           float* sig_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Independent sessions on one Mimi stream state: pushes of a SUBSET of its B streams ("slots").  The state is
+ * prepared whole by ac_mimi_stream_reset / _decode_reset (that call writes the header and registers the address, for the capacity B);
+ * a slot restarts alone through the same call with a reset mask, and the calls below run any of the slots while the others keep what
+ * they hold.
+ *   slots_host [n]  the slot list in host memory: 1 <= n <= B distinct values in [0, B).  The library reads it for every check, all
+ *                   decided before anything is launched.
+ *   slots_dev  [n]  the caller's device copy of the same list, which the kernels read (the library neither allocates nor copies).
+ *                   Whatever it holds, the kernels index only inside the state: an entry outside [0, B) makes that row touch no state.
+ * Row i of sig_dev [n, F * hop] / toks_dev [n, F, K] belongs to slot slots_host[i], each at its own position (conv caches, K/V rings
+ * and the position go through the list; every activation stays dense).  Every buffer, scale and launch is that of a lockstep push of
+ * B = n streams, so the workspace is ac_mimi_stream_workspace_bytes(h, n, F) / _decode_workspace_bytes(h, n, F), and the bits of a
+ * slot's result are those of the lockstep stream of batch n fed the same rows: they depend neither on the slot's index, nor on the
+ * order of the list, nor on what the other rows or the unlisted slots carry.  (The decode side picks the route of its linear layers
+ * from the dense row count n * F * resample_stride, as ac_mimi_stream_decode does from B: "mstream_skinny" in ac_debug_set.)  Mimi
+ * pads with zeros: fresh and warm slots share any call at any F >= 1, and the handle keeps no per-slot record.  A lockstep push on the
+ * same state is the push of all B slots in order.
+ * AC_EINVAL for a state never reset on this handle, reset as the other kind or for another B, n outside [1, B], a slot outside [0, B)
+ * or listed twice, a null pointer, K or F out of range, a non-Mimi handle; AC_ENOMEM for a short state or workspace; AC_ESTATE for a
+ * handle loaded without the half it needs.  After a refusal the handle and the state are as they were; nothing allocates or
+ * synchronises. */
+int ac_mimi_stream_encode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev,
+                                int n, const float* sig_dev, int F, int K, int64_t* toks_dev, void* workspace_dev,
+                                size_t workspace_bytes, void* stream);
+int ac_mimi_stream_decode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev,
+                                int n, const int64_t* toks_dev, int F, int K, float* sig_dev, void* workspace_dev,
+                                size_t workspace_bytes, void* stream);
+
 /* Streaming EnCodec encode and decode: the same contract as the Mimi calls above on an EnCodec handle -- B streams, F whole frames per
  * stream and push, tokens [B,F,K] and samples [B, F * hop] in ac_encode's / ac_decode's layouts; the caller owns the state
  * (ac_encodec_stream_state_bytes / _decode_state_bytes(h, B) bytes, 256-byte aligned) and the workspace (_workspace_bytes(h, B, F));
