@@ -56,6 +56,7 @@ struct ResBlockPlan {
     size_t w3p_off = 0, wfp_off = 0;       // rb_stream6.h (C = 64): the same images with every k-step's 32 columns in the lanes' load order
     float hb0 = 0.f, hb1 = 0.f;            // split16.h: |hidden| <= hb0 + hb1 * amax(x)
     bool has6 = false;
+    bool hb256 = false;                    // C = 256: hb0 / hb1 are set for rb256_fused.h (its images are the tap-GEMM's: w6_of)
 };
 
 struct LstmPlan {
@@ -192,6 +193,7 @@ struct ac_handle {
         int tap8_spread = 1;        // AC_TAP8_SPREAD=0|1|2: tap_gemm8's requests of a stage at its top / dealt between its MFMA units where that measured faster (128-row tiles) / dealt everywhere (bit-identical)
         int rb6_dbg = 0;            // AC_RB6_DBG          : timing variants of the fused blocks (wrong results)
         int rb_stream = 1;          // AC_RB_STREAM=0      : the 64-channel causal blocks through rb_fused6.h instead of rb_stream6.h (A/B, cross-check tests)
+        int rb256_fused = 1;        // AC_RB256_FUSED=0    : EnCodec's 256-channel blocks as two tap-GEMM launches instead of rb256_fused.h (A/B, cross-check tests)
         int rb128_stream = 1;       // AC_RB128_STREAM=0   : Mimi's 128-channel identity blocks through rb128_fused6 instead of rb_stream128m.h
         int chain_stream = 1;       // AC_CHAIN_STREAM=0   : the fused thin-channel chains through enc_front.h / dec_tail.h instead of enc_stream.h / dec_stream.h
         int front_seg = 0, tail_seg = 0;   // AC_FRONT_SEG / AC_TAIL_SEG: chunks per stream of the fused chains (0: from the batch size)
@@ -496,6 +498,18 @@ struct Packer {
     // rb_fused6.h images of a residual block (k3 conv C -> C/2, then [1x1 over the hidden | optional shortcut over x])
     void rb6(ResBlockPlan& rb, bool sc) {
         const int C = rb.C, hid = C / 2;
+        if (C == 256 && sc && use16() && rb.c3.N == hid && rb.c3.Ktot == 3 * C && rb.fused.N == C && rb.fused.Ktot == hid + C && rb.c3.has_bias && rb.fused.has_bias) {
+            // rb256_fused.h runs on the tap-GEMM images of the two matrices; what it needs beyond them is the hidden activation's bound
+            rb.hb0 = rb.hb1 = 0.f;
+            for (int n = 0; n < hid; ++n) {
+                double l1 = 0.0;
+                for (int k = 0; k < rb.c3.Ktot; ++k) l1 += std::fabs((double)blob[rb.c3.w_off + (size_t)n * rb.c3.Ktot + k]);
+                rb.hb1 = std::max(rb.hb1, (float)(l1 * 1.000001));
+                rb.hb0 = std::max(rb.hb0, std::fabs(blob[rb.c3.b_off + n]));
+            }
+            rb.hb256 = true;
+            return;
+        }
         if ((C != 32 && C != 64 && C != 128) || rb.c3.N != hid || rb.c3.Ktot != 3 * C || rb.fused.N != C || rb.fused.Ktot != hid + (sc ? C : 0)) return;
         std::vector<int> k3(3 * C), kf;
         for (int k = 0; k < 3 * C; ++k) k3[k] = k;
@@ -896,6 +910,7 @@ int convtr_fwd(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, 
 bool rb128_ok(const ac_handle* h, const ResBlockPlan& rb);
 
 int resblock_fwd(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Act2& x, float* hbuf, Out out, int B, Act2* y);
+bool rb256_ok(const ac_handle* h, const ResBlockPlan& rb, int L);
 
 bool thin_ok(const ac_config& c, int k);
 

@@ -15,6 +15,7 @@
 #include "rb_fused6.h"
 #include "thin_conv6.h"
 #include "rb_fused6_128.h"
+#include "rb256_fused.h"
 #include "enc_front.h"
 #include "dec_tail.h"
 
@@ -634,6 +635,70 @@ int launch_rb128_fused6(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, co
 bool rb128_ok(const ac_handle* h, const ResBlockPlan& rb) { return rb.C == 128 && rb.has6 && !h->gemm_fp32; }
 
 
+// can EnCodec's 256-channel block run as one kernel (rb256_fused.h)?  (the producer then writes the raw flavour only)
+// L: time rows per clip of the block's input -- at least one tile of the kernel
+bool rb256_ok(const ac_handle* h, const ResBlockPlan& rb, int L) {
+    if (!h->dev.rb256_fused || rb.C != 256 || !rb.hb256 || h->gemm_fp32 || h->noncausal || h->cfg.residual_kernel_size != 3 || h->cfg.compress != 2 || L < Rb256Cfg::BM ||
+        (long long)L * 1024 >= 0x70000000LL)
+        return false;
+    return h->w6_of.count(rb.c3.w_off) && h->winv_of.count(rb.c3.w_off) && h->w6_of.count(rb.fused.w_off) && h->winv_of.count(rb.fused.w_off);
+}
+
+int launch_rb256_fused(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Act2& x, Out out, int B, Act2* y) {
+    using Cfg = Rb256Cfg;
+    const int L = x.raw.L;
+    const unsigned* am = amax_of(h, st, x.raw.p, x.raw.bs, x.raw.ts, L, 256, B, x.raw.amax_n == B ? x.raw.amax : nullptr);
+    if (!am) return fail(h, AC_ESTATE, "out of amax slots (split16.h)");
+    Act xr = x.raw;
+    xr.amax = am;
+    xr.amax_n = B;
+    Rb256Params q{};
+    TapGemmParams& a = q.a;
+    a.nseg = 1;
+    a.seg[0] = make_seg(xr, 1, 3, PAD_REFLECT, 0, 0, nullptr);
+    a.w = h->blob + rb.c3.w_off;
+    a.bias = h->blob + rb.c3.b_off;
+    a.winv = h->blob + h->winv_of.at(rb.c3.w_off);
+    a.B = B;
+    a.M = L;
+    a.N = rb.c3.N;
+    a.Ktot = rb.c3.Ktot;
+    a.mtiles = cdiv(L, Cfg::BM);
+    a.ntiles = 1;
+    TapGemmParams& b = q.b;
+    b.nseg = 1;
+    b.seg[0] = make_seg(xr, 1, 1, PAD_REFLECT, 0, rb.c3.N, nullptr);
+    b.w = h->blob + rb.fused.w_off;
+    b.bias = h->blob + rb.fused.b_off;
+    b.winv = h->blob + h->winv_of.at(rb.fused.w_off);
+    b.y = out.raw;
+    b.y_elu = out.elu;
+    b.y_bs = (long long)L * 256;
+    b.y_rs = 256;
+    b.B = B;
+    b.M = L;
+    b.N = 256;
+    b.Ktot = rb.fused.Ktot;
+    b.mtiles = a.mtiles;
+    b.ntiles = 1;
+    b.amax_out = amax_new(h);
+    b.epi_direct = h->dev.tap_epi_staged ? 0 : 1;     // (as route_tap decides for the two-launch path's second launch)
+    q.hb0 = rb.hb0;
+    q.hb1 = rb.hb1;
+    if (int rc = ensure_lds(h, reinterpret_cast<const void*>(rb256_fused_kernel), Cfg::lds_bytes)) return rc;
+    {
+        ProfScope ps(h, st, "rb256_fused_kernel", 2.0 * B * (double)L * (128.0 * 768 + 256.0 * 384),
+                     (double)B * L * 256 * 4.0 * (1 + (out.raw ? 1 : 0) + (out.elu ? 1 : 0)) + (128.0 * 768 + 256.0 * 384) * 4.0);
+        hipLaunchKernelGGL(rb256_fused_kernel, dim3((unsigned)((long long)B * a.mtiles)), dim3(Cfg::NT), Cfg::lds_bytes, st, q,
+                           reinterpret_cast<const __bf16*>(h->blob + h->w6_of.at(rb.c3.w_off)), reinterpret_cast<const __bf16*>(h->blob + h->w6_of.at(rb.fused.w_off)));
+    }
+    HIPCHK(h, hipGetLastError());
+    y->raw = Act{out.raw, b.y_bs, 256, L, 256, b.amax_out, B};
+    y->elu = Act{out.elu, b.y_bs, 256, L, 256, b.amax_out, B};
+    return AC_OK;
+}
+
+
 // ResBlock: hbuf = ELU(conv3(ELU(x)));  out = [hbuf | x] * [W1; Ws] + (b1 + bs)
 int resblock_fwd(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Act2& x, float* hbuf, Out out, int B, Act2* y) {
     if (rb128_ok(h, rb) && h->cfg.residual_kernel_size == 3 && h->cfg.compress == 2 && x.raw.ts == 128 &&
@@ -647,6 +712,9 @@ int resblock_fwd(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Act
         y->elu = Act{out.elu, bs, 128, x.raw.L, 128, am, B};
         return AC_OK;
     }
+    if (rb256_ok(h, rb, x.raw.L) && x.raw.ts == 256 && x.raw.bs == (long long)x.raw.L * 256 && aligned16(x.raw.p) && (out.raw == nullptr || aligned16(out.raw)) &&
+        aligned16(out.elu))
+        return launch_rb256_fused(h, st, rb, x, out, B, y);
     // thin stages: one fused kernel, hidden activation never leaves the CU
     // (rb_fused.h, the exact-product version, knows the causal halo only)
     if ((rb.C == 32 || rb.C == 64) && !(h->noncausal && (!rb.has6 || h->gemm_fp32)) && h->cfg.residual_kernel_size == 3 && h->cfg.compress == 2 && x.raw.ts == rb.C &&
@@ -663,6 +731,7 @@ int resblock_fwd(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Act
         y->elu = Act{out.elu, bs, rb.C, x.raw.L, rb.C, am, B};
         return AC_OK;
     }
+    if (!x.elu.p) return fail(h, AC_ESTATE, "residual block: the two-launch path needs the ELU'd flavour of its input");
     Act2 hv;
     int rc = conv_fwd(h, st, rb.c3, x.elu, h->cfg.residual_kernel_size, 1, nullptr, Out{nullptr, hbuf},
                       (long long)x.elu.L * rb.c3.N, rb.c3.N, B, &hv);
@@ -1284,6 +1353,8 @@ int encoder_fwd(ac_handle* h, hipStream_t st, const float* sig, const float* rel
         if (h->noncausal && h->gemm_fp32) return false;   // non-causal blocks are fused in split-operand arithmetic only
         return (C == 32 || C == 64 || (C == 128 && c.num_ratios > 2 && rb128_ok(h, h->enc_rb[2]))) && c.residual_kernel_size == 3 && c.compress == 2;
     };
+    // ... and so does a 256-channel block that runs as one kernel (rb256_fused.h); L: the rows the producer writes
+    auto rb256_self_elu = [&](int i, int L) { return i < c.num_ratios && h->enc_rb[i].C == h->enc_down[i - 1].N && rb256_ok(h, h->enc_rb[i], L); };
     int i0 = 0;
     if (enc_front_ok(h, T)) {   // stem, first residual block and first down-sampler as one kernel (enc_front.h)
         float* d0 = dbg ? ws.take() : nullptr;
@@ -1319,7 +1390,7 @@ int encoder_fwd(ac_handle* h, hipStream_t st, const float* sig, const float* rel
         const int M = cdiv(x.elu.L, ratio);
         const bool last = i == c.num_ratios - 1;    // the last down-sampler feeds the LSTM: raw only
         rc = conv_fwd(h, st, h->enc_down[i], x.elu, 2 * ratio, ratio, nullptr,
-                      Out{ws.take(), (last || rb_self_elu(h->enc_down[i].N)) ? nullptr : ws.take()},
+                      Out{ws.take(), (last || rb_self_elu(h->enc_down[i].N) || rb256_self_elu(i + 1, M)) ? nullptr : ws.take()},
                       (long long)M * h->enc_down[i].N, h->enc_down[i].N, B, &y);
         if (rc) return rc;
         ws.give(x);
@@ -1372,8 +1443,9 @@ int decoder_fwd(ac_handle* h, hipStream_t st, const long long* toks, int B, int 
             return AC_OK;
         }
         const int cup = h->dec_up[i].N / c.upsampling_ratios[i];
-        const bool self_elu = (cup == 32 || cup == 64 || (cup == 128 && rb128_ok(h, h->dec_rb[i]))) && c.residual_kernel_size == 3 &&
-                              c.compress == 2;   // rb_fused.h / rb_fused6*.h activate raw rows themselves
+        const bool self_elu = ((cup == 32 || cup == 64 || (cup == 128 && rb128_ok(h, h->dec_rb[i]))) && c.residual_kernel_size == 3 &&
+                               c.compress == 2) ||   // rb_fused.h / rb_fused6*.h activate raw rows themselves
+                              (cup == h->dec_rb[i].C && rb256_ok(h, h->dec_rb[i], x.elu.L * c.upsampling_ratios[i]));     // ... and so does rb256_fused.h
         rc = convtr_fwd(h, st, h->dec_up[i], x.elu, c.upsampling_ratios[i], Out{ws.take(), self_elu ? nullptr : ws.take()}, B, &y);
         if (rc) return rc;
         ws.give(x);

@@ -351,6 +351,7 @@ __device__ __forceinline__ void tap6_epilogue(const TapGemmParams& p, f32x16 (&a
 struct Tap6Tile {
     int b, m0, n0;
     float a_inv;
+    float a_scale;      // FUSE = 2 only, with a_inv: the operand scale the caller chose
     bool rowmode;
     unsigned long long clk_t0, clk_r0;
     bool t6_ph;
@@ -359,14 +360,17 @@ struct Tap6Tile {
 // ---- the main loop of a tile (prologue, K loop): tap_gemm6_kernel = this + tap6_epilogue; dac_unit6_kernel (dac_unit6.h) = this with
 // SWAP + a second product + tap6_epilogue.  SWAP: the MFMA's operands exchanged -- the accumulators hold the TRANSPOSED 32 x 32 tiles
 // (lane = row of the tile, register r = column 8 (r / 4) + 4 kh + r % 4), same products, same order.
-template <int WGM, int WGN, int WMT, int WN, int HALO, bool SWAP>
+// FUSE (rb256_fused.h runs two main loops on one tile): 1 = the rows are activated (ELU) while they are staged; 2 = the accumulators
+// arrive with the products of an earlier K range in them and the operand scale is the caller's (tl.a_scale, tl.a_inv).
+template <int WGM, int WGN, int WMT, int WN, int HALO, bool SWAP, int FUSE = 0>
 __device__ __forceinline__ void tap6_mainloop(const TapGemmParams& p, const __bf16* __restrict__ wp, float* smem, f32x16 (&acc)[WMT][WN], Tap6Tile& tl) {
     constexpr int NP = 2;
     using Cfg = Tap6Cfg<WGM, WGN, WMT, WN, HALO>;
     constexpr int BM = Cfg::BM, BN = Cfg::BN, NT = Cfg::NT, A_SLOTS = Cfg::A_SLOTS, PLANE = Cfg::PLANE;
     unsigned long long clk_t0 = 0, clk_r0 = 0;
-    if (p.clk) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
-    if (p.stagger && (int)blockIdx.x < 256 * tap6_occupancy<WGM, WGN, WMT, WN, NP>()) {
+    if (FUSE == 2) { clk_t0 = tl.clk_t0; clk_r0 = tl.clk_r0; }
+    else if (p.clk) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
+    if (FUSE != 2 && p.stagger && (int)blockIdx.x < 256 * tap6_occupancy<WGM, WGN, WMT, WN, NP>()) {
         const unsigned long long wait = (unsigned long long)((blockIdx.x * 0x9E3779B1u) >> 24) * (unsigned)p.stagger >> 8;
         const unsigned long long t0 = __builtin_amdgcn_s_memtime();
         while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(32);
@@ -402,12 +406,14 @@ __device__ __forceinline__ void tap6_mainloop(const TapGemmParams& p, const __bf
     T6_PHASE(1);
 #endif
 
+    if constexpr (FUSE != 2) {
 #pragma unroll
-    for (int a = 0; a < WMT; ++a)
+        for (int a = 0; a < WMT; ++a)
 #pragma unroll
-        for (int c = 0; c < WN; ++c)
+            for (int c = 0; c < WN; ++c)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][c][r] = 0.f;
+                for (int r = 0; r < 16; ++r) acc[a][c][r] = 0.f;
+    }
 
     // slot i of a thread = element tid + i * NT of the slab = (row tid / 8 + (NT / 8) i, 16-byte column tid % 8): the LDS offsets of a
     // thread's slots are NT / 8 rows apart (ONE register + constants; a per-slot array cost the 128 x 32 arrangement three spilled
@@ -477,7 +483,10 @@ __device__ __forceinline__ void tap6_mainloop(const TapGemmParams& p, const __bf
         am_rows[i] = p.seg[0].amax[rowmode ? (m < p.M ? m : p.M - 1) : 0];
     }
     auto set_scales = [&]() {
-        if (!rowmode) {
+        if constexpr (FUSE == 2) {
+            a_scale = tl.a_scale;
+            a_inv = tl.a_inv;
+        } else if (!rowmode) {
             // (through a VGPR-constrained asm: hipcc otherwise moves the wave-uniform words to SGPRs -- v_readfirstlane, and the wait with it --
             //  right behind their loads)
             unsigned a0 = am_e0, a1 = am_e1;
@@ -535,7 +544,8 @@ __device__ __forceinline__ void tap6_mainloop(const TapGemmParams& p, const __bf
 #pragma unroll
         for (int i = 0; i < A_SLOTS; ++i)
             if (i + 1 < A_SLOTS || last_slot_ok) {
-                const f32x4 v = (a_zero & (1u << i)) ? f32x4{0.f, 0.f, 0.f, 0.f} : ra[i];
+                f32x4 v = (a_zero & (1u << i)) ? f32x4{0.f, 0.f, 0.f, 0.f} : ra[i];
+                if constexpr (FUSE == 1) v = elu4(v);
                 split16_store4s(v, a_rsc[CAN_ROWMODE ? i : 0], dst, PLANE, a_lds0 + i * (NT / (KC / 4)) * T6_PITCH);
             }
     };
