@@ -12,7 +12,8 @@ import os
 
 import torch  # noqa: F401  (loads libamdhip64 first)
 
-__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS"]
+__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
+           "Handle", "HandleOwner"]
 
 AC_MAX_RATIOS = 8
 # AUDIOCODECS_AMD_LIB: developer override (timing variants built by hand); the product is the in-tree library
@@ -255,7 +256,6 @@ def track(obj) -> None:
     _live.add(obj)
 
 
-
 def lib():
     """Load (once) and return the library; raises NativeError when it has not been built."""
     global _lib
@@ -278,3 +278,92 @@ def check(rc: int, handle=None, what: str = "") -> None:
     if rc < 0:
         msg = lib().ac_last_error(handle).decode() if handle else ""
         raise NativeError(f"{what} failed with code {rc}: {msg}")
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class Handle:
+    """One ac_handle: weights on one GPU + a grow-only workspace tensor.  `create` names the codec's `ac_*create`, `cfg` is its config
+    struct with the architecture filled in (struct_size and device are set here), `hint` what a refusal most likely means; every
+    floating-point tensor of `weights` is loaded under its name."""
+
+    def __init__(self, create: str, cfg, hint: str, weights, device: torch.device, precision=None):
+        self.lib = lib()
+        cfg.struct_size = C.sizeof(cfg)
+        cfg.device = device.index if device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", cfg.device)
+        self.h = C.c_void_p()
+        rc = getattr(self.lib, create)(C.byref(cfg), C.byref(self.h))
+        if rc < 0:
+            raise NativeError(f"{create} failed with code {rc} ({hint})")
+        set_precision(self.lib, self.h, precision)
+        for name, t in weights.items():
+            if not torch.is_tensor(t) or not t.is_floating_point():
+                continue
+            t = t.detach().to(torch.float32).cpu().contiguous()
+            check(self.lib.ac_load_weights(self.h, name.encode(), C.c_void_p(t.data_ptr()), t.numel() * 4), self.h, f"ac_load_weights({name})")
+        with torch.cuda.device(self.device):
+            check(self.lib.ac_finalize(self.h), self.h, "ac_finalize")
+        self.ws = None
+        track(self)
+
+    def workspace(self, nbytes: int) -> torch.Tensor:
+        if self.ws is None or self.ws.numel() < nbytes:
+            self.ws = None
+            self.ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        return self.ws
+
+    def __del__(self):
+        try:
+            import sys
+
+            if sys.is_finalizing():   # interpreter shutdown: the HIP runtime may already be gone, the OS reclaims the rest
+                return
+            if getattr(self, "h", None):
+                self.lib.ac_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+class HandleOwner:
+    """What the four wrappers share: one lazily created `Handle` per device in `self._natives` (device index -> handle).  A wrapper
+    states only how its handle is built (`_new_handle`)."""
+
+    def _new_handle(self, device: torch.device) -> Handle:
+        raise NotImplementedError
+
+    def _native_for(self, t: torch.Tensor) -> Handle:
+        if not t.is_cuda:
+            raise NativeError(
+                "audiocodecs_amd runs on MI355X only: move the input to a cuda device "
+                "(there is deliberately no CPU fallback)"
+            )
+        idx = t.device.index
+        if idx not in self._natives:
+            self._natives[idx] = self._new_handle(t.device)
+        return self._natives[idx]
+
+    def _any_native(self) -> Handle:
+        """A handle that exists, or one on the current device."""
+        dev = next(iter(self._natives.values())).device if self._natives else torch.device("cuda", torch.cuda.current_device())
+        return self._native_for(torch.empty(0, device=dev))
+
+    # ---- measurement hook used by bench.py ------------------------------------------------------
+    def profile_kernels(self, fn):
+        """Run fn() with per-kernel HIP-event timing armed; returns [(name, launches, ms, flops, bytes)]."""
+        nat = self._any_native()
+        check(nat.lib.ac_profile_begin(nat.h), nat.h, "ac_profile_begin")
+        try:
+            fn()
+        finally:
+            buf = (AcKernelStat * 256)()
+            n = nat.lib.ac_profile_end(nat.h, buf, 256)
+        check(n, nat.h, "ac_profile_end")
+        return [(buf[i].name.decode(), buf[i].launches, buf[i].total_ms, buf[i].flops, buf[i].bytes) for i in range(n)]

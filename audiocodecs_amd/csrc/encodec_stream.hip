@@ -356,18 +356,6 @@ static int estream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int 
     return AC_OK;
 }
 
-// a slot list (host memory): 1 <= n <= B entries in [0, B), none twice
-static int estream_slots_check(ac_handle* h, const int* slots, int n, int B, const char* who) {
-    if (n < 1 || n > B) return fail(h, AC_EINVAL, "%s: n=%d slots of a state of %d", who, n, B);
-    std::vector<uint8_t> seen((size_t)B, 0);
-    for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= B) return fail(h, AC_EINVAL, "%s: slot %d outside [0, %d)", who, slots[i], B);
-        if (seen[slots[i]]) return fail(h, AC_EINVAL, "%s: slot %d listed twice", who, slots[i]);
-        seen[slots[i]] = 1;
-    }
-    return AC_OK;
-}
-
 // the handle's record of a state of `B` streams, and its layout, or the refusal
 static int estream_find(ac_handle* h, void* state_dev, size_t state_bytes, int B, bool dec, const char* who, EStreamLayout* Ls,
                         ac_handle::EStreamReg** reg) {
@@ -396,7 +384,7 @@ static int estream_push_check(ac_handle* h, void* state_dev, size_t state_bytes,
     const std::vector<uint8_t>& fresh = (*reg)->fresh;
     bool any_fresh = false;
     if (slots) {
-        if ((rc = estream_slots_check(h, slots, n, B, who))) return rc;
+        if ((rc = stream_slots_check(h, slots, n, B, who))) return rc;
         for (int i = 0; i < n; ++i) any_fresh = any_fresh || fresh[slots[i]];
     } else {
         for (int b = 0; b < B; ++b) any_fresh = any_fresh || fresh[b];
@@ -417,7 +405,7 @@ static int estream_reset_slots(ac_handle* h, void* state_dev, size_t state_bytes
     EStreamLayout Ls;
     ac_handle::EStreamReg* reg = nullptr;
     if ((rc = estream_find(h, state_dev, state_bytes, B, dec, who, &Ls, &reg))) return rc;
-    if ((rc = estream_slots_check(h, slots_host, n, B, who))) return rc;
+    if ((rc = stream_slots_check(h, slots_host, n, B, who))) return rc;
     const LstmPlan& lp = dec ? h->dec_lstm : h->enc_lstm;
     char* s = static_cast<char*>(state_dev);
     hipStream_t st = (hipStream_t)stream;
@@ -463,12 +451,6 @@ static int estream_decode(ac_handle* h, void* state_dev, size_t state_bytes, int
     if (!rc)
         for (int i = 0; i < n; ++i) reg->fresh[slots_host ? slots_host[i] : i] = 0;
     return rc;
-}
-
-// a slot call's own arguments (the rest is the push's); a null handle falls through to the push's check
-static int eslots_args(ac_handle* h, const int* slots_host, const int* slots_dev, const char* who) {
-    if (h && (!slots_host || !slots_dev)) return fail(h, AC_EINVAL, "%s: the slot list is null", who);
-    return AC_OK;
 }
 
 }  // namespace acimpl
@@ -528,14 +510,14 @@ int ac_encodec_stream_decode_reset_slots(ac_handle* h, void* state_dev, size_t s
 int ac_encodec_stream_encode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
                                    const float* sig_dev, int F, int K, int64_t* toks_dev, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "ac_encodec_stream_encode_slots";
-    const int rc = eslots_args(h, slots_host, slots_dev, who);
+    const int rc = stream_slots_args(h, slots_host, slots_dev, who);
     return rc ? rc : estream_encode(h, state_dev, state_bytes, B, slots_host, slots_dev, n, sig_dev, F, K, toks_dev, ws, ws_bytes, stream, who);
 }
 
 int ac_encodec_stream_decode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
                                    const int64_t* toks_dev, int F, int K, float* sig_dev, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "ac_encodec_stream_decode_slots";
-    const int rc = eslots_args(h, slots_host, slots_dev, who);
+    const int rc = stream_slots_args(h, slots_host, slots_dev, who);
     return rc ? rc : estream_decode(h, state_dev, state_bytes, B, slots_host, slots_dev, n, toks_dev, F, K, sig_dev, ws, ws_bytes, stream, who);
 }
 

@@ -399,21 +399,24 @@ static int mstream_check(ac_handle* h, int B, bool dec = false) {
     return AC_OK;
 }
 
-// a slot list (host memory): 1 <= n <= B entries in [0, B), none twice
-static int mstream_slots_check(ac_handle* h, const int* slots, int n, int B, const char* who) {
-    if (n < 1 || n > B) return fail(h, AC_EINVAL, "%s: n=%d slots of a state of %d", who, n, B);
-    std::vector<uint8_t> seen((size_t)B, 0);
-    for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= B) return fail(h, AC_EINVAL, "%s: slot %d outside [0, %d)", who, slots[i], B);
-        if (seen[slots[i]]) return fail(h, AC_EINVAL, "%s: slot %d listed twice", who, slots[i]);
-        seen[slots[i]] = 1;
-    }
-    return AC_OK;
-}
-
-// a slot call's own arguments (the rest is the push's); a null handle falls through to the push's check
-static int mslots_args(ac_handle* h, const int* slots_host, const int* slots_dev, const char* who) {
-    if (h && (!slots_host || !slots_dev)) return fail(h, AC_EINVAL, "%s: the slot list is null", who);
+// The checks of a push that touch nothing, in the order both directions make them; *Ls: the state's layout.
+static int mstream_push_check(ac_handle* h, void* state_dev, size_t state_bytes, const void* in, const void* out, int B, const int* slots_host, int n,
+                              int F, int K, bool dec, const char* who, MStreamLayout* Ls) {
+    int rc = mstream_check(h, B, dec);
+    if (rc) return rc;
+    if (!state_dev || !in || !out || F < 1) return fail(h, AC_EINVAL, "%s: bad argument (F=%d)", who, F);
+    if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "%s: K=%d outside [1, %d]", who, K, h->mcfg.num_quantizers);
+    const auto& mine = dec ? h->mimi_dstreams : h->mimi_streams;
+    const auto& other = dec ? h->mimi_streams : h->mimi_dstreams;
+    auto it = mine.find(state_dev);
+    if (it == mine.end())
+        return fail(h, AC_EINVAL, "%s: the state was never reset%s on this handle%s", who, dec ? " as a decode state" : "",
+                    !other.count(state_dev) ? "" : dec ? " (it is an encode state)" : " as an encode state (it is a decode state)");
+    if (it->second != B) return fail(h, AC_EINVAL, "%s: the state holds %d streams, B=%d", who, it->second, B);
+    *Ls = dec ? mdstream_layout(h, B) : mstream_layout(h, B);
+    if (state_bytes < Ls->total) return fail(h, AC_ENOMEM, "%s: state of %zu bytes, %zu needed", who, state_bytes, Ls->total);
+    if ((long long)F * h->hop > 0x7fffffffLL / 64) return fail(h, AC_EINVAL, "%s: F=%d frames per push is too many", who, F);
+    if (slots_host && (rc = stream_slots_check(h, slots_host, n, B, who))) return rc;
     return AC_OK;
 }
 
@@ -422,18 +425,9 @@ static int mslots_args(ac_handle* h, const int* slots_host, const int* slots_dev
 // state.  Mimi pads with zeros: a fresh stream takes any F >= 1, and the host keeps no per-slot record.
 static int mstream_encode(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
                           const float* sig_dev, int F, int K, int64_t* toks_dev, void* ws, size_t ws_bytes, void* stream, const char* who) {
-    int rc = mstream_check(h, B);
+    MStreamLayout Ls;
+    int rc = mstream_push_check(h, state_dev, state_bytes, sig_dev, toks_dev, B, slots_host, n, F, K, false, who, &Ls);
     if (rc) return rc;
-    if (!state_dev || !sig_dev || !toks_dev || F < 1) return fail(h, AC_EINVAL, "%s: bad argument (F=%d)", who, F);
-    if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "%s: K=%d outside [1, %d]", who, K, h->mcfg.num_quantizers);
-    auto it = h->mimi_streams.find(state_dev);
-    if (it == h->mimi_streams.end())
-        return fail(h, AC_EINVAL, "%s: the state was never reset on this handle%s", who, h->mimi_dstreams.count(state_dev) ? " as an encode state (it is a decode state)" : "");
-    if (it->second != B) return fail(h, AC_EINVAL, "%s: the state holds %d streams, B=%d", who, it->second, B);
-    const MStreamLayout Ls = mstream_layout(h, B);
-    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "%s: state of %zu bytes, %zu needed", who, state_bytes, Ls.total);
-    if ((long long)F * h->hop > 0x7fffffffLL / 64) return fail(h, AC_EINVAL, "%s: F=%d frames per push is too many", who, F);
-    if (slots_host && (rc = mstream_slots_check(h, slots_host, n, B, who))) return rc;
     const Workspace w = mstream_plan_ws(h, n, F);
     WsPtrs p;
     if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
@@ -452,19 +446,9 @@ static int mstream_encode(ac_handle* h, void* state_dev, size_t state_bytes, int
 
 static int mstream_decode(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
                           const int64_t* toks_dev, int F, int K, float* sig_dev, void* ws, size_t ws_bytes, void* stream, const char* who) {
-    int rc = mstream_check(h, B, true);
+    MStreamLayout Ls;
+    int rc = mstream_push_check(h, state_dev, state_bytes, toks_dev, sig_dev, B, slots_host, n, F, K, true, who, &Ls);
     if (rc) return rc;
-    if (!state_dev || !sig_dev || !toks_dev || F < 1) return fail(h, AC_EINVAL, "%s: bad argument (F=%d)", who, F);
-    if (K < 1 || K > h->mcfg.num_quantizers) return fail(h, AC_EINVAL, "%s: K=%d outside [1, %d]", who, K, h->mcfg.num_quantizers);
-    auto it = h->mimi_dstreams.find(state_dev);
-    if (it == h->mimi_dstreams.end())
-        return fail(h, AC_EINVAL, "%s: the state was never reset as a decode state on this handle%s", who,
-                    h->mimi_streams.count(state_dev) ? " (it is an encode state)" : "");
-    if (it->second != B) return fail(h, AC_EINVAL, "%s: the state holds %d streams, B=%d", who, it->second, B);
-    const MStreamLayout Ls = mdstream_layout(h, B);
-    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "%s: state of %zu bytes, %zu needed", who, state_bytes, Ls.total);
-    if ((long long)F * h->hop > 0x7fffffffLL / 64) return fail(h, AC_EINVAL, "%s: F=%d frames per push is too many", who, F);
-    if (slots_host && (rc = mstream_slots_check(h, slots_host, n, B, who))) return rc;
     const Workspace w = mdstream_plan_ws(h, n, F);
     WsPtrs p;
     if ((rc = carve(h, w, ws, ws_bytes, &p))) return rc;
@@ -474,6 +458,29 @@ static int mstream_decode(ac_handle* h, void* state_dev, size_t state_bytes, int
     const int sw = h->dev.mstream_skinny;
     const bool skinny = sw > 0 || (sw < 0 && rows <= MSTREAM_SKINNY_AUTO_ROWS);
     return mstream_decoder(h, st, static_cast<char*>(state_dev), Ls, slots_dev, reinterpret_cast<const long long*>(toks_dev), n, F, K, sig_dev, p, w.act_floats, skinny);
+}
+
+// ac_mimi_stream_reset / _decode_reset: the header, and position = 0, fresh = 1 for every stream or the masked ones
+static int mstream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, const uint8_t* reset_mask_dev, void* stream, bool dec) {
+    const char* who = dec ? "ac_mimi_stream_decode_reset" : "ac_mimi_stream_reset";
+    int rc = mstream_check(h, B, dec);
+    if (rc) return rc;
+    if (!state_dev) return fail(h, AC_EINVAL, "%s: state is null", who);
+    const MStreamLayout Ls = dec ? mdstream_layout(h, B) : mstream_layout(h, B);
+    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "%s: state of %zu bytes, %zu needed", who, state_bytes, Ls.total);
+    if ((reinterpret_cast<uintptr_t>(state_dev) & 255) != 0) return fail(h, AC_EINVAL, "%s: state must be 256-byte aligned", who);
+    auto& mine = dec ? h->mimi_dstreams : h->mimi_streams;
+    auto it = mine.find(state_dev);
+    if (reset_mask_dev && (it == mine.end() || it->second != B))
+        return fail(h, AC_EINVAL, "%s: a masked reset needs a %sstate this handle reset for B=%d before", who, dec ? "decode " : "", B);
+    char* s = static_cast<char*>(state_dev);
+    MStreamHeader hd{dec ? MDSTREAM_MAGIC : MSTREAM_MAGIC, 1u, mstream_fingerprint(h->mcfg), B, 0};
+    hipLaunchKernelGGL(mstream_reset_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<MStreamHeader*>(s), hd,
+                       reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh), reset_mask_dev, B);
+    HIPCHK(h, hipGetLastError());
+    mine[state_dev] = B;
+    (dec ? h->mimi_streams : h->mimi_dstreams).erase(state_dev);      // (the header just written ends its life as the other kind)
+    return AC_OK;
 }
 
 }  // namespace acimpl
@@ -493,23 +500,7 @@ size_t ac_mimi_stream_workspace_bytes(const ac_handle* h, int B, int F) {
 }
 
 int ac_mimi_stream_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, const uint8_t* reset_mask_dev, void* stream) {
-    int rc = mstream_check(h, B);
-    if (rc) return rc;
-    if (!state_dev) return fail(h, AC_EINVAL, "ac_mimi_stream_reset: state is null");
-    const MStreamLayout Ls = mstream_layout(h, B);
-    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "ac_mimi_stream_reset: state of %zu bytes, %zu needed", state_bytes, Ls.total);
-    if ((reinterpret_cast<uintptr_t>(state_dev) & 255) != 0) return fail(h, AC_EINVAL, "ac_mimi_stream_reset: state must be 256-byte aligned");
-    auto it = h->mimi_streams.find(state_dev);
-    if (reset_mask_dev && (it == h->mimi_streams.end() || it->second != B))
-        return fail(h, AC_EINVAL, "ac_mimi_stream_reset: a masked reset needs a state this handle reset for B=%d before", B);
-    char* s = static_cast<char*>(state_dev);
-    MStreamHeader hd{MSTREAM_MAGIC, 1u, mstream_fingerprint(h->mcfg), B, 0};
-    hipLaunchKernelGGL(mstream_reset_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<MStreamHeader*>(s), hd,
-                       reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh), reset_mask_dev, B);
-    HIPCHK(h, hipGetLastError());
-    h->mimi_streams[state_dev] = B;
-    h->mimi_dstreams.erase(state_dev);      // (the header just written makes it an encode state)
-    return AC_OK;
+    return mstream_reset(h, state_dev, state_bytes, B, reset_mask_dev, stream, false);
 }
 
 int ac_mimi_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, const float* sig_dev, int B, int F, int K, int64_t* toks_dev,
@@ -520,7 +511,7 @@ int ac_mimi_stream_encode(ac_handle* h, void* state_dev, size_t state_bytes, con
 int ac_mimi_stream_encode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
                                 const float* sig_dev, int F, int K, int64_t* toks_dev, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "ac_mimi_stream_encode_slots";
-    const int rc = mslots_args(h, slots_host, slots_dev, who);
+    const int rc = stream_slots_args(h, slots_host, slots_dev, who);
     return rc ? rc : mstream_encode(h, state_dev, state_bytes, B, slots_host, slots_dev, n, sig_dev, F, K, toks_dev, ws, ws_bytes, stream, who);
 }
 
@@ -535,23 +526,7 @@ size_t ac_mimi_stream_decode_workspace_bytes(const ac_handle* h, int B, int F) {
 }
 
 int ac_mimi_stream_decode_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, const uint8_t* reset_mask_dev, void* stream) {
-    int rc = mstream_check(h, B, true);
-    if (rc) return rc;
-    if (!state_dev) return fail(h, AC_EINVAL, "ac_mimi_stream_decode_reset: state is null");
-    const MStreamLayout Ls = mdstream_layout(h, B);
-    if (state_bytes < Ls.total) return fail(h, AC_ENOMEM, "ac_mimi_stream_decode_reset: state of %zu bytes, %zu needed", state_bytes, Ls.total);
-    if ((reinterpret_cast<uintptr_t>(state_dev) & 255) != 0) return fail(h, AC_EINVAL, "ac_mimi_stream_decode_reset: state must be 256-byte aligned");
-    auto it = h->mimi_dstreams.find(state_dev);
-    if (reset_mask_dev && (it == h->mimi_dstreams.end() || it->second != B))
-        return fail(h, AC_EINVAL, "ac_mimi_stream_decode_reset: a masked reset needs a decode state this handle reset for B=%d before", B);
-    char* s = static_cast<char*>(state_dev);
-    MStreamHeader hd{MDSTREAM_MAGIC, 1u, mstream_fingerprint(h->mcfg), B, 0};
-    hipLaunchKernelGGL(mstream_reset_kernel<>, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<MStreamHeader*>(s), hd,
-                       reinterpret_cast<long long*>(s + Ls.pos), reinterpret_cast<int*>(s + Ls.fresh), reset_mask_dev, B);
-    HIPCHK(h, hipGetLastError());
-    h->mimi_dstreams[state_dev] = B;
-    h->mimi_streams.erase(state_dev);       // (the header just written makes it a decode state)
-    return AC_OK;
+    return mstream_reset(h, state_dev, state_bytes, B, reset_mask_dev, stream, true);
 }
 
 int ac_mimi_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, const int64_t* toks_dev, int B, int F, int K, float* sig_dev,
@@ -562,7 +537,7 @@ int ac_mimi_stream_decode(ac_handle* h, void* state_dev, size_t state_bytes, con
 int ac_mimi_stream_decode_slots(ac_handle* h, void* state_dev, size_t state_bytes, int B, const int* slots_host, const int* slots_dev, int n,
                                 const int64_t* toks_dev, int F, int K, float* sig_dev, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "ac_mimi_stream_decode_slots";
-    const int rc = mslots_args(h, slots_host, slots_dev, who);
+    const int rc = stream_slots_args(h, slots_host, slots_dev, who);
     return rc ? rc : mstream_decode(h, state_dev, state_bytes, B, slots_host, slots_dev, n, toks_dev, F, K, sig_dev, ws, ws_bytes, stream, who);
 }
 

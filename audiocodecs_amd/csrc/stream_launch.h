@@ -9,6 +9,24 @@ static unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n 
 
 static Act staged_act(const float* p, int B, int rows, int C) { return Act{p, (long long)rows * C, C, rows, C}; }
 
+// a slot list (host memory): 1 <= n <= B entries in [0, B), none twice
+static int stream_slots_check(ac_handle* h, const int* slots, int n, int B, const char* who) {
+    if (n < 1 || n > B) return fail(h, AC_EINVAL, "%s: n=%d slots of a state of %d", who, n, B);
+    std::vector<uint8_t> seen((size_t)B, 0);
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= B) return fail(h, AC_EINVAL, "%s: slot %d outside [0, %d)", who, slots[i], B);
+        if (seen[slots[i]]) return fail(h, AC_EINVAL, "%s: slot %d listed twice", who, slots[i]);
+        seen[slots[i]] = 1;
+    }
+    return AC_OK;
+}
+
+// a slot call's own arguments (the rest is the push's); a null handle falls through to the push's check
+static int stream_slots_args(ac_handle* h, const int* slots_host, const int* slots_dev, const char* who) {
+    if (h && (!slots_host || !slots_dev)) return fail(h, AC_EINVAL, "%s: the slot list is null", who);
+    return AC_OK;
+}
+
 // [cache | x] -> staged (a fresh activation buffer of B * (P + L) * C floats); x's last P rows -> cache.  `cache` [B][P][C] and
 // `fresh` [B] live in the stream state; `mode` (STAGE_*) is a fresh stream's history.  `slot` (device, [B]; null = identity): the push's
 // row b addresses stream slot[b] of the `slot_cap` streams the state holds; x and staged stay dense.

@@ -11,7 +11,6 @@ own backend is unpinned (oracle/dac_oracle.py header).
 
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
@@ -19,7 +18,7 @@ import torch
 from . import _native
 from .codec import Codec
 from .config import DAC_16KHZ, DAC_24KHZ, DAC_44KHZ, DacConfig
-from .encodec import _ptr, _stream
+from ._native import Handle, _ptr, _stream
 
 __all__ = ["DAC", "state_dict_from_descript"]
 
@@ -59,67 +58,22 @@ def state_dict_from_descript(sd: Dict[str, torch.Tensor], cfg: DacConfig) -> Dic
     return out
 
 
-class _NativeDac:
-    """One DAC ac_handle: weights on one GPU + a grow-only workspace tensor."""
-
-    def __init__(self, cfg: DacConfig, sd: Dict[str, torch.Tensor], device: torch.device, precision=None):
-        self.lib = _native.lib()
-        c = _native.AcDacConfig()
-        c.struct_size = C.sizeof(_native.AcDacConfig)
-        c.sampling_rate = cfg.sampling_rate
-        c.encoder_hidden_size = cfg.encoder_hidden_size
-        c.decoder_hidden_size = cfg.decoder_hidden_size
-        c.num_ratios = len(cfg.downsampling_ratios)
-        for i, r in enumerate(cfg.downsampling_ratios):
-            c.downsampling_ratios[i] = r
-        for i, r in enumerate(cfg.upsampling_ratios):
-            c.upsampling_ratios[i] = r
-        c.n_codebooks = cfg.n_codebooks
-        c.codebook_size = cfg.codebook_size
-        c.codebook_dim = cfg.codebook_dim
-        c.num_dilations = len(cfg.dilations)
-        for i, d in enumerate(cfg.dilations):
-            c.dilations[i] = d
-        c.device = device.index if device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", c.device)
-        self.h = C.c_void_p()
-        rc = self.lib.ac_dac_create(C.byref(c), C.byref(self.h))
-        if rc < 0:
-            raise _native.NativeError(f"ac_dac_create failed with code {rc} (unsupported configuration, or no gfx950 GPU visible)")
-        _native.set_precision(self.lib, self.h, precision)
-        for name, t in sd.items():
-            if not t.is_floating_point():
-                continue
-            t = t.detach().to(torch.float32).cpu().contiguous()
-            _native.check(
-                self.lib.ac_load_weights(self.h, name.encode(), C.c_void_p(t.data_ptr()), t.numel() * 4),
-                self.h, f"ac_load_weights({name})",
-            )
-        with torch.cuda.device(self.device):
-            _native.check(self.lib.ac_finalize(self.h), self.h, "ac_finalize")
-        self.ws: Optional[torch.Tensor] = None
-        _native.track(self)
-
-    def workspace(self, nbytes: int) -> torch.Tensor:
-        if self.ws is None or self.ws.numel() < nbytes:
-            self.ws = None
-            self.ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-        return self.ws
-
-    def __del__(self):
-        try:
-            import sys
-
-            if sys.is_finalizing():   # interpreter shutdown: the HIP runtime may already be gone, the OS reclaims the rest
-                return
-            if getattr(self, "h", None):
-                self.lib.ac_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+def _handle(cfg: DacConfig, sd: Dict[str, torch.Tensor], device: torch.device, precision=None) -> Handle:
+    c = _native.AcDacConfig()
+    for f in ("sampling_rate", "encoder_hidden_size", "decoder_hidden_size", "n_codebooks", "codebook_size", "codebook_dim"):
+        setattr(c, f, getattr(cfg, f))
+    c.num_ratios = len(cfg.downsampling_ratios)
+    for i, r in enumerate(cfg.downsampling_ratios):
+        c.downsampling_ratios[i] = r
+    for i, r in enumerate(cfg.upsampling_ratios):
+        c.upsampling_ratios[i] = r
+    c.num_dilations = len(cfg.dilations)
+    for i, d in enumerate(cfg.dilations):
+        c.dilations[i] = d
+    return Handle("ac_dac_create", c, "unsupported configuration, or no gfx950 GPU visible", sd, device, precision)
 
 
-class DAC(Codec):
+class DAC(_native.HandleOwner, Codec):
     _accepts_none_length = True
 
     def __init__(
@@ -158,21 +112,10 @@ class DAC(Codec):
         if any(k.endswith("weight_g") for k in state_dict):
             state_dict = state_dict_from_descript(state_dict, config)
         self._sd = dict(state_dict)
-        self._natives: Dict[int, _NativeDac] = {}
+        self._natives: Dict[int, Handle] = {}
 
-    def _native_for(self, t: torch.Tensor) -> _NativeDac:
-        if not t.is_cuda:
-            raise _native.NativeError(
-                "audiocodecs_amd runs on MI355X only: move the input to a cuda device (there is deliberately no CPU fallback)"
-            )
-        idx = t.device.index
-        if idx not in self._natives:
-            self._natives[idx] = _NativeDac(self.config, self._sd, t.device, self.precision)
-        return self._natives[idx]
-
-    def _any_native(self) -> _NativeDac:
-        dev = next(iter(self._natives.values())).device if self._natives else torch.device("cuda", torch.cuda.current_device())
-        return self._native_for(torch.empty(0, device=dev))
+    def _new_handle(self, device: torch.device) -> Handle:
+        return _handle(self.config, self._sd, device, self.precision)
 
     def _K(self) -> int:
         # dac/nn/quantize.py: the loop breaks at i >= n_quantizers, so asking for more than exist uses them all
@@ -266,15 +209,3 @@ class DAC(Codec):
                 nat.h, "ac_decode",
             )
         return sig
-
-    # ---- measurement hook used by bench.py ------------------------------------------------------
-    def profile_kernels(self, fn):
-        nat = self._any_native()
-        _native.check(nat.lib.ac_profile_begin(nat.h), nat.h, "ac_profile_begin")
-        try:
-            fn()
-        finally:
-            buf = (_native.AcKernelStat * 256)()
-            n = nat.lib.ac_profile_end(nat.h, buf, 256)
-        _native.check(n, nat.h, "ac_profile_end")
-        return [(buf[i].name.decode(), buf[i].launches, buf[i].total_ms, buf[i].flops, buf[i].bytes) for i in range(n)]

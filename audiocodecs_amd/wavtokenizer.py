@@ -11,7 +11,6 @@ PyTorch is used for device memory and streams only.
 
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Dict, Optional
 
@@ -20,65 +19,24 @@ import torch
 from . import _native
 from .codec import Codec
 from .config import WAVTOK_40, WAVTOK_75, WavTokenizerConfig
-from .encodec import _ptr, _stream
+from ._native import Handle, _ptr, _stream
 
 __all__ = ["WavTokenizer"]
 
 
-class _NativeWavTok:
-    """One WavTokenizer ac_handle: weights on one GPU + a grow-only workspace tensor."""
-
-    def __init__(self, cfg: WavTokenizerConfig, sd: Dict[str, torch.Tensor], device: torch.device, precision=None):
-        self.lib = _native.lib()
-        c = _native.AcWavtokConfig()
-        c.struct_size = C.sizeof(_native.AcWavtokConfig)
-        for f in ("sampling_rate", "num_filters", "dimension", "kernel_size", "last_kernel_size", "residual_kernel_size", "compress",
-                  "num_lstm_layers", "codebook_size", "backbone_dim", "intermediate_dim", "num_layers", "adanorm_num_embeddings",
-                  "num_groups", "n_fft", "bandwidth_id"):
-            setattr(c, f, getattr(cfg, f))
-        c.num_ratios = len(cfg.ratios)
-        for i, r in enumerate(cfg.ratios):
-            c.ratios[i] = r
-        c.device = device.index if device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", c.device)
-        self.h = C.c_void_p()
-        rc = self.lib.ac_wavtok_create(C.byref(c), C.byref(self.h))
-        if rc < 0:
-            raise _native.NativeError(f"ac_wavtok_create failed with code {rc} (unsupported configuration, or no gfx950 GPU visible)")
-        _native.set_precision(self.lib, self.h, precision)
-        for name, t in sd.items():
-            if not torch.is_tensor(t) or not t.is_floating_point():
-                continue
-            t = t.detach().to(torch.float32).cpu().contiguous()
-            _native.check(
-                self.lib.ac_load_weights(self.h, name.encode(), C.c_void_p(t.data_ptr()), t.numel() * 4),
-                self.h, f"ac_load_weights({name})",
-            )
-        with torch.cuda.device(self.device):
-            _native.check(self.lib.ac_finalize(self.h), self.h, "ac_finalize")
-        self.ws: Optional[torch.Tensor] = None
-        _native.track(self)
-
-    def workspace(self, nbytes: int) -> torch.Tensor:
-        if self.ws is None or self.ws.numel() < nbytes:
-            self.ws = None
-            self.ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-        return self.ws
-
-    def __del__(self):
-        try:
-            import sys
-
-            if sys.is_finalizing():
-                return
-            if getattr(self, "h", None):
-                self.lib.ac_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+def _handle(cfg: WavTokenizerConfig, sd: Dict[str, torch.Tensor], device: torch.device, precision=None) -> Handle:
+    c = _native.AcWavtokConfig()
+    for f in ("sampling_rate", "num_filters", "dimension", "kernel_size", "last_kernel_size", "residual_kernel_size", "compress",
+              "num_lstm_layers", "codebook_size", "backbone_dim", "intermediate_dim", "num_layers", "adanorm_num_embeddings",
+              "num_groups", "n_fft", "bandwidth_id"):
+        setattr(c, f, getattr(cfg, f))
+    c.num_ratios = len(cfg.ratios)
+    for i, r in enumerate(cfg.ratios):
+        c.ratios[i] = r
+    return Handle("ac_wavtok_create", c, "unsupported configuration, or no gfx950 GPU visible", sd, device, precision)
 
 
-class WavTokenizer(Codec):
+class WavTokenizer(_native.HandleOwner, Codec):
     _accepts_none_length = True
     _graph_capable = False        # codec.py: the persistent LSTM launch is not replayable from a hipGraph
     SOURCES = [
@@ -134,7 +92,7 @@ class WavTokenizer(Codec):
         elif mode == "decode":
             sd = {k: v for k, v in sd.items() if not k.startswith("feature_extractor.encodec.encoder.")}
         self._sd = sd
-        self._natives: Dict[int, _NativeWavTok] = {}
+        self._natives: Dict[int, Handle] = {}
 
     @staticmethod
     def _fetch_pretrained(source: str, checkpoint: str):
@@ -146,21 +104,8 @@ class WavTokenizer(Codec):
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         return ckpt.get("state_dict", ckpt)
 
-    # ------------------------------------------------------------------------------------------
-    def _native_for(self, t: torch.Tensor) -> _NativeWavTok:
-        if not t.is_cuda:
-            raise _native.NativeError(
-                "audiocodecs_amd runs on MI355X only: move the input to a cuda device "
-                "(there is deliberately no CPU fallback)"
-            )
-        idx = t.device.index
-        if idx not in self._natives:
-            self._natives[idx] = _NativeWavTok(self.arch, self._sd, t.device, self.precision)
-        return self._natives[idx]
-
-    def _any_native(self) -> _NativeWavTok:
-        dev = next(iter(self._natives.values())).device if self._natives else torch.device("cuda", torch.cuda.current_device())
-        return self._native_for(torch.empty(0, device=dev))
+    def _new_handle(self, device: torch.device) -> Handle:
+        return _handle(self.arch, self._sd, device, self.precision)
 
     # override
     @torch.no_grad()
@@ -260,15 +205,3 @@ class WavTokenizer(Codec):
                 nat.h, "ac_decode_feats",
             )
         return sig
-
-    # ---- measurement hook used by bench.py ------------------------------------------------------
-    def profile_kernels(self, fn):
-        nat = self._any_native()
-        _native.check(nat.lib.ac_profile_begin(nat.h), nat.h, "ac_profile_begin")
-        try:
-            fn()
-        finally:
-            buf = (_native.AcKernelStat * 256)()
-            n = nat.lib.ac_profile_end(nat.h, buf, 256)
-        _native.check(n, nat.h, "ac_profile_end")
-        return [(buf[i].name.decode(), buf[i].launches, buf[i].total_ms, buf[i].flops, buf[i].bytes) for i in range(n)]

@@ -1,6 +1,6 @@
 """Session pools on EnCodec streams, the part that needs no GPU: the grouping rule (audiocodecs_amd/sessions.py plan_push) against
-a per-row simulation of the rule a lockstep stream applies to itself (encodec.py EncodecEncodeStream._take /
-EncodecDecodeStream._decode), and the null-handle answers of the four slot entry points."""
+a per-row simulation of the rule a lockstep stream applies to itself (streams.py LockstepStream._take, both directions),
+and the null-handle answers of the four slot entry points."""
 import ctypes as C
 
 import numpy as np

@@ -1,6 +1,6 @@
 """Session pools on Mimi streams, the part that needs no GPU: the grouping rule (audiocodecs_amd/sessions.py plan_push) with
 warmup = 1 -- Mimi pads with zeros, so a fresh slot runs its first whole frame at once -- against a per-row simulation of the rule a
-lockstep stream applies to itself (mimi.py MimiEncodeStream._take / MimiDecodeStream._decode), and the null-handle answers of the two
+lockstep stream applies to itself (streams.py LockstepStream._take, both directions), and the null-handle answers of the two
 slot entry points."""
 import ctypes as C
 
