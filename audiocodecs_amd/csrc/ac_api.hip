@@ -722,6 +722,46 @@ int ac_resample_stream_push(void* state_dev, size_t state_bytes, const float* x_
                                        (hipStream_t)stream);
 }
 
+// the slot forms: a host list of 1 <= n_rows <= B distinct slots in [0, B); counts[r] >= 0 where given
+static bool rstream_slots_ok(const int* slots, int n_rows, int B) {
+    if (!slots || n_rows < 1 || n_rows > B) return false;
+    std::vector<uint8_t> seen((size_t)B, 0);
+    for (int r = 0; r < n_rows; ++r) {
+        if (slots[r] < 0 || slots[r] >= B || seen[slots[r]]) return false;
+        seen[slots[r]] = 1;
+    }
+    return true;
+}
+
+int ac_resample_stream_reset_slots(void* state_dev, size_t state_bytes, int B, int n, int o, int taps, int width, const int* slots_host,
+                                   const int* slots_dev, int n_rows, void* stream) {
+    if (!state_dev || (reinterpret_cast<uintptr_t>(state_dev) & 255) != 0 || !slots_dev || !rstream_geometry_ok(B, n, o, taps, width)) return AC_EINVAL;
+    if (!rstream_slots_ok(slots_host, n_rows, B)) return AC_EINVAL;
+    if (state_bytes < resample_stream_state_bytes(B, taps)) return AC_ENOMEM;
+    return resample_stream_reset_slots_launch(state_dev, B, n, o, taps, width, slots_dev, n_rows, (hipStream_t)stream);
+}
+
+int ac_resample_stream_push_slots(void* state_dev, size_t state_bytes, int B, const int* slots_host, const long long* consumed_host,
+                                  const int* slots_dev, const long long* consumed_dev, int n_rows, const float* x_dev, long long x_pitch, int L,
+                                  const float* kern_dev, int n, int o, int taps, int width, float* y_dev, long long y_pitch, long long y_capacity,
+                                  int finish, void* stream) {
+    if (!state_dev || (reinterpret_cast<uintptr_t>(state_dev) & 255) != 0 || !kern_dev || !rstream_geometry_ok(B, n, o, taps, width)) return AC_EINVAL;
+    if (!consumed_host || !slots_dev || !consumed_dev || !rstream_slots_ok(slots_host, n_rows, B)) return AC_EINVAL;
+    if (L < 0 || (L > 0 && (!x_dev || x_pitch < L))) return AC_EINVAL;
+    long long m = 0;
+    for (int r = 0; r < n_rows; ++r) {
+        const long long m_r = ac_resample_stream_out_len(consumed_host[r], L, n, o, width, finish);   // (refuses a negative count)
+        if (m_r < 0 || m_r > 0x7fffffffll - 256) return AC_EINVAL;
+        m = std::max(m, m_r);
+    }
+    if (m > 0 && (!y_dev || y_pitch < m)) return AC_EINVAL;
+    if (state_bytes < resample_stream_state_bytes(B, taps)) return AC_ENOMEM;
+    if (y_capacity < m) return AC_ENOMEM;
+    if (L == 0 && !finish) return AC_OK;          // nothing to take in, nothing complete: the state stays as it is
+    return resample_stream_push_slots_launch(state_dev, B, slots_dev, consumed_dev, n_rows, x_dev, x_pitch, L, kern_dev, n, o, taps, width, y_dev, y_pitch,
+                                             (int)m, finish ? 1 : 0, (hipStream_t)stream);
+}
+
 const char* ac_last_error(const ac_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
 void ac_destroy(ac_handle* h) {

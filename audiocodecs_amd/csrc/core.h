@@ -1023,6 +1023,11 @@ size_t resample_stream_state_bytes(int B, int taps);
 int resample_stream_reset_launch(void* state, int B, int n, int o, int taps, int width, hipStream_t st);
 int resample_stream_push_launch(void* state, const float* x, long long x_pitch, int B, int L, long long consumed, const float* kern, int n, int o, int taps,
                                 int width, float* y, long long y_pitch, int m, int finish, hipStream_t st);
+// the slot forms: `rows` listed slots of a state of B, each at its own count; m is the largest row's output length
+int resample_stream_reset_slots_launch(void* state, int B, int n, int o, int taps, int width, const int* slots_dev, int rows, hipStream_t st);
+int resample_stream_push_slots_launch(void* state, int B, const int* slots_dev, const long long* consumed_dev, int rows, const float* x, long long x_pitch,
+                                      int L, const float* kern, int n, int o, int taps, int width, float* y, long long y_pitch, int m, int finish,
+                                      hipStream_t st);
 
 // ---- per-codec paths (mimi_path.hip, dac_path.hip, wavtok_path.hip)
 // optional epilogue terms of a tap-GEMM launch (Mimi's transformers, WavTokenizer's backbone, DAC's residual units)

@@ -1614,6 +1614,24 @@ int resample_stream_push_launch(void* state, const float* x, long long x_pitch, 
     hipLaunchKernelGGL(resample_stream_hist_kernel, dim3(B), dim3(256), sizeof(float) * (size_t)(taps - 1), st, p);
     return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
 }
+int resample_stream_reset_slots_launch(void* state, int B, int n, int o, int taps, int width, const int* slots_dev, int rows, hipStream_t st) {
+    char* s = static_cast<char*>(state);
+    const RStreamHeader hd{RSTREAM_MAGIC, B, n, o, taps, width};
+    hipLaunchKernelGGL(resample_slots_reset_kernel, dim3(rows), dim3(256), 0, st, reinterpret_cast<const RStreamHeader*>(s), hd,
+                       reinterpret_cast<long long*>(s + 256), reinterpret_cast<float*>(s + 256 + rstream_align(sizeof(long long) * (size_t)B)), slots_dev);
+    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+}
+int resample_stream_push_slots_launch(void* state, int B, const int* slots_dev, const long long* consumed_dev, int rows, const float* x, long long x_pitch,
+                                      int L, const float* kern, int n, int o, int taps, int width, float* y, long long y_pitch, int m, int finish,
+                                      hipStream_t st) {
+    char* s = static_cast<char*>(state);
+    ResampleSlotsParams p{x, kern, y, reinterpret_cast<const RStreamHeader*>(s), reinterpret_cast<long long*>(s + 256),
+                          reinterpret_cast<float*>(s + 256 + rstream_align(sizeof(long long) * (size_t)B)), slots_dev, consumed_dev,
+                          x_pitch, y_pitch, rows, B, L, m, n, o, taps, width, finish};
+    if (m > 0) hipLaunchKernelGGL(resample_slots_kernel, dim3((unsigned)((m + 255) / 256), rows), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(resample_slots_hist_kernel, dim3(rows), dim3(256), sizeof(float) * (size_t)(taps - 1), st, p);
+    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+}
 void amax_fill_launch(hipStream_t st, unsigned* slot, unsigned bits, int B) {
     hipLaunchKernelGGL(amax_fill_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, slot, bits, B);
 }

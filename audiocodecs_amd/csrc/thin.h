@@ -245,6 +245,19 @@ __device__ __forceinline__ bool rstream_state_ok(const ResampleStreamParams& p, 
            p.consumed[b] == p.before;
 }
 
+// One output of a push: filter row kr [taps] over (hb [taps - 1] ++ xb [L]).  `base` is the position of tap 0 relative to the chunk's first
+// sample; >= -(taps - 1) because the output's group was not complete before this push.
+__device__ __forceinline__ float rstream_dot(const float* kr, const float* hb, const float* xb, int base, int taps, int L) {
+    const int H = taps - 1;
+    float acc = 0.f;
+    for (int k = 0; k < taps; ++k) {       // ascending k, one fmaf per tap: resample_kernel's chain (a stored zero where it skips)
+        const int m = base + k;
+        if (m < 0) acc = fmaf(kr[k], hb[H + m], acc);
+        else if (m < L) acc = fmaf(kr[k], xb[m], acc);
+    }
+    return acc;
+}
+
 __global__ __launch_bounds__(256) void resample_stream_kernel(const ResampleStreamParams p) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
@@ -258,18 +271,8 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const ResampleStre
     const long long i = gid / p.n;
     const int ph = (int)(gid % p.n);
     const int H = p.taps - 1;
-    const float* xb = p.x + (long long)b * p.x_pitch;
-    const float* hb = p.hist + (long long)b * H;
-    const float* kr = p.kern + (long long)ph * p.taps;
-    // position of tap 0 relative to the chunk's first sample; >= -H because group i was not complete before this push
-    const int base = (int)(i * p.o - p.width - p.before);
-    float acc = 0.f;
-    for (int k = 0; k < p.taps; ++k) {     // ascending k, one fmaf per tap: resample_kernel's chain (a stored zero where it skips)
-        const int m = base + k;
-        if (m < 0) acc = fmaf(kr[k], hb[H + m], acc);
-        else if (m < p.L) acc = fmaf(kr[k], xb[m], acc);
-    }
-    yb[j] = acc;
+    yb[j] = rstream_dot(p.kern + (long long)ph * p.taps, p.hist + (long long)b * H, p.x + (long long)b * p.x_pitch,
+                        (int)(i * p.o - p.width - p.before), p.taps, p.L);
 }
 
 __global__ __launch_bounds__(256) void resample_stream_hist_kernel(const ResampleStreamParams p) {
@@ -296,6 +299,95 @@ __global__ __launch_bounds__(256) void resample_stream_reset_kernel(RStreamHeade
         consumed[b] = 0;
         if (b == 0) *hdr = hd;
     }
+}
+
+// The slot forms (ac_resample_stream_*_slots): the same state, a push of a SUBSET of its streams, each at its own
+// phase.  Row r of the push belongs to slot[r] and continues from before[r], that slot's count as the caller holds it; the row derives
+// its out0 = n * G(before[r]) and its own length m_r by the rule above, so the rows of one call emit different numbers of samples (the
+// grid is sized by the largest, `m`, and no row writes past it).  slot[] and before[] are the caller's device copies: whatever they hold,
+// a row whose slot is outside [0, B), whose count is negative or not the state's, or whose header differs, writes NaN to its outputs and
+// touches no state, and the kernels index only inside the state and the first m floats of a y row.  Per output the chain is
+// resample_stream_kernel's (rstream_dot); the history moves on one workgroup per listed row, and workgroup r is the only writer of
+// consumed[slot[r]] and hist[slot[r]] (the host refuses a list that names a slot twice).
+struct ResampleSlotsParams {
+    const float* x;          // [rows][x_pitch]: L new samples per listed slot
+    const float* kern;       // [n][taps]
+    float* y;                // [rows][y_pitch]: row r's m_r outputs
+    const RStreamHeader* hdr;
+    long long* consumed;     // [B]
+    float* hist;             // [B][taps - 1]
+    const int* slot;         // [rows] (device)
+    const long long* before; // [rows] (device): samples slot[r] consumed before this push
+    long long x_pitch, y_pitch;
+    int rows, B, L, m, n, o, taps, width, finish;
+};
+
+__device__ __forceinline__ long long rstream_groups(long long total, int o, int width) {
+    return total < (long long)width + o ? 0 : (total - width - o) / o + 1;
+}
+
+// row r's slot, or -1 when the row must not touch the state
+__device__ __forceinline__ int rslots_row(const ResampleSlotsParams& p, int r, long long before) {
+    const RStreamHeader h = *p.hdr;
+    const int s = p.slot[r];
+    if (h.magic != RSTREAM_MAGIC || h.B != p.B || h.n != p.n || h.o != p.o || h.taps != p.taps || h.width != p.width) return -1;
+    if (s < 0 || s >= p.B || before < 0 || before > (1ll << 62) / p.n - p.L) return -1;
+    return p.consumed[s] == before ? s : -1;
+}
+
+__global__ __launch_bounds__(256) void resample_slots_kernel(const ResampleSlotsParams p) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int r = blockIdx.y;
+    if (j >= p.m) return;
+    float* yr = p.y + (long long)r * p.y_pitch;
+    const long long before = p.before[r];
+    long long out0 = 0, m_r = p.m;                       // (a count that is not a count: the row's own length is unknown, all m are NaN)
+    if (before >= 0 && before <= (1ll << 62) / p.n - p.L) {
+        const long long total = before + p.L;
+        out0 = p.n * rstream_groups(before, p.o, p.width);
+        m_r = (p.finish ? (p.n * total + p.o - 1) / p.o : p.n * rstream_groups(total, p.o, p.width)) - out0;
+    }
+    if (j >= m_r) return;                                // behind m_r: left as it is
+    const int s = rslots_row(p, r, before);
+    if (s < 0) {
+        yr[j] = __builtin_nanf("");
+        return;
+    }
+    const long long gid = out0 + j;
+    const long long i = gid / p.n;
+    const int H = p.taps - 1;
+    yr[j] = rstream_dot(p.kern + (gid % p.n) * p.taps, p.hist + (long long)s * H, p.x + (long long)r * p.x_pitch,
+                        (int)(i * p.o - p.width - before), p.taps, p.L);
+}
+
+__global__ __launch_bounds__(256) void resample_slots_hist_kernel(const ResampleSlotsParams p) {
+    extern __shared__ __align__(16) float rs_row[];      // [taps - 1]
+    const int r = blockIdx.x;
+    const long long before = p.before[r];
+    const int s = rslots_row(p, r, before);
+    if (s < 0) return;                                   // (uniform over the workgroup)
+    const int H = p.taps - 1;
+    const float* xr = p.x + (long long)r * p.x_pitch;
+    float* hb = p.hist + (long long)s * H;
+    for (int j = threadIdx.x; j < H; j += 256) {
+        const long long q = (long long)j + p.L;
+        rs_row[j] = q < H ? hb[q] : xr[q - H];
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < H; j += 256) hb[j] = rs_row[j];
+    if (threadIdx.x == 0) p.consumed[s] = p.finish ? RSTREAM_FINISHED : before + p.L;
+}
+
+// the listed slots start afresh; the header is compared, never written (one workgroup per row)
+__global__ __launch_bounds__(256) void resample_slots_reset_kernel(const RStreamHeader* hdr, const RStreamHeader hd, long long* consumed, float* hist,
+                                                                   const int* slot) {
+    const RStreamHeader h = *hdr;
+    const int s = slot[blockIdx.x];
+    if (h.magic != hd.magic || h.B != hd.B || h.n != hd.n || h.o != hd.o || h.taps != hd.taps || h.width != hd.width) return;
+    if (s < 0 || s >= hd.B) return;
+    float* hb = hist + (long long)s * (hd.taps - 1);
+    for (int j = threadIdx.x; j < hd.taps - 1; j += 256) hb[j] = 0.f;
+    if (threadIdx.x == 0) consumed[s] = 0;
 }
 
 }  // namespace ac

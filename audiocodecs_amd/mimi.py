@@ -198,15 +198,17 @@ class Mimi(_native.HandleOwner, Codec):
         `ResampleStream` behind the decoder (`finish` returns its tail)."""
         return MimiDecodeStream(self, self._stream_checks("decode_stream", batch_size, device, resample), batch_size, bool(resample))
 
-    def encode_sessions(self, capacity: int, device=None) -> "MimiEncodeSessions":
+    def encode_sessions(self, capacity: int, device=None, *, resample: bool = False) -> "MimiEncodeSessions":
         """A pool of up to `capacity` independent encode sessions on one stream state: sessions `open` and `close` at any time and
         `push(slots, sig)` serves any subset of them, each at its own position and with the bits of a lone `encode_stream(1)`
-        (DESIGN.md section 8g).  Runs at the codec's own rate only."""
-        return MimiEncodeSessions(self, self._stream_checks("encode_sessions", capacity, device), capacity)
+        (DESIGN.md section 8g).  `resample=True`: the pushes are at `sample_rate` and pass a `ResampleSlots` to the codec's
+        rate first, every session at its own phase (section 8h; close a session's signal with `finish(slot)`)."""
+        return MimiEncodeSessions(self, self._stream_checks("encode_sessions", capacity, device, resample), capacity, bool(resample))
 
-    def decode_sessions(self, capacity: int, device=None) -> "MimiDecodeSessions":
-        """The decode side of `encode_sessions`: `push(slots, toks)` returns every listed session's samples."""
-        return MimiDecodeSessions(self, self._stream_checks("decode_sessions", capacity, device), capacity)
+    def decode_sessions(self, capacity: int, device=None, *, resample: bool = False) -> "MimiDecodeSessions":
+        """The decode side of `encode_sessions`: `push(slots, toks)` returns every listed session's samples.  `resample=True`: they
+        come out at `sample_rate`, through a `ResampleSlots` behind the decoder (`finish(slot)` returns a session's tail)."""
+        return MimiDecodeSessions(self, self._stream_checks("decode_sessions", capacity, device, resample), capacity, bool(resample))
 
 
 class _OnMimi:
@@ -257,13 +259,18 @@ class MimiDecodeStream(_OnMimi, LockstepStream):
 class MimiEncodeSessions(_OnMimi, SessionPool):
     """A pool of encode sessions on one Mimi stream state (Mimi.encode_sessions; include/audiocodecs_amd.h ac_mimi_stream_*_slots).
     `push(slots, sig)`: `sig` is [n, L] fp32 on the codec's device, any L >= 0; returns n int64 tensors [f_i, K], the tokens of the
-    frames each slot completes.  Partial frames wait per slot; there is no warm-up hold."""
+    frames each slot completes.  Partial frames wait per slot; there is no warm-up hold.  With `resample=True` on a codec at
+    another rate, `sig` is at `sample_rate` and passes a `ResampleSlots` first, every slot at its own phase: frames, `pending` and
+    the hold count resampled samples; `finish(slot)` flushes that slot's resampler and returns the tokens of any frame it completes,
+    after which the slot accepts only `close`."""
 
     _kind = "encode"
 
 
 class MimiDecodeSessions(_OnMimi, SessionPool):
     """A pool of decode sessions (Mimi.decode_sessions).  `push(slots, toks)`: `toks` is [n, F, K] int64 on the codec's device,
-    K = the codec's `num_codebooks`, any F >= 0; returns n fp32 tensors [F * hop], the samples of each slot's frames."""
+    K = the codec's `num_codebooks`, any F >= 0; returns n fp32 tensors [F * hop], the samples of each slot's frames.  With `resample=True`
+    on a codec at another rate the samples pass a `ResampleSlots` to `sample_rate` on their way out: a push returns what each slot's
+    resampler completed, `finish(slot)` its tail (`toks_to_sig`'s length in all), after which the slot accepts only `close`."""
 
     _kind = "decode"

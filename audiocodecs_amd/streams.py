@@ -84,7 +84,7 @@ def stream_checks(codec, name: str, what: str, n, device, resample: bool, valida
     if codec.sample_rate != codec.config.sampling_rate and not resample:
         raise ValueError(
             f"{what} runs at the codec's own rate ({codec.config.sampling_rate} Hz): streaming resampling from or to "
-            f"sample_rate={codec.sample_rate} is " + ("not available per slot" if pool else "opt-in, pass resample=True")
+            f"sample_rate={codec.sample_rate} is opt-in, pass resample=True"
         )
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
         raise ValueError(f"`{'capacity' if pool else 'batch_size'}` ({n!r}) must be a positive int")

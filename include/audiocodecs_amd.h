@@ -453,6 +453,35 @@ int ac_resample_stream_push(void* state_dev, size_t state_bytes, const float* x_
                             const float* kern_dev, int n, int o, int taps, int width, float* y_dev, long long y_pitch, long long y_capacity,
                             int finish, void* stream);
 
+/* Independent sessions on one resampler state: pushes and resets of a SUBSET of its B streams ("slots"), each at its own phase
+ * (DESIGN.md section 8h).  The state is the one above, prepared whole by ac_resample_stream_reset (that call alone writes the header),
+ * and serves both forms.
+ *   slots_host [n_rows], consumed_host [n_rows]  the slot list (1 <= n_rows <= B distinct values in [0, B)) and, per listed slot, the
+ *                   caller's count of the samples it has consumed, in host memory.  The library reads them for every check and to size
+ *                   the grid, all decided before anything is launched.
+ *   slots_dev [n_rows], consumed_dev [n_rows]    the caller's device copies, which the kernels read (the library neither allocates nor
+ *                   copies; both may lie in one buffer, so that one host-to-device copy brings them).  Whatever they hold, the kernels
+ *                   index only inside the state and the first max_r m_r floats of a y row: a row whose slot is outside [0, B), or whose
+ *                   count is negative or not the state's, gets NaN outputs and touches no state.
+ * ac_resample_stream_reset_slots: the listed slots start afresh (count 0, zero history) in one launch; no other byte of the state
+ * changes, and nothing at all when the header is not that of the arguments.
+ * ac_resample_stream_push_slots: row r of x_dev brings L samples to slot slots_host[r] and emits
+ * m_r = ac_resample_stream_out_len(consumed_host[r], L, n, o, width, finish) samples into y_dev[r][0 .. m_r); m_r differs between the rows
+ * of one call, and what lies behind m_r in a row is left untouched.  L and finish hold for every row of the call.  Per output the fp32
+ * chain is ac_resample_stream_push's, so a slot's pushes and its closing push, concatenated, are ac_resample of its whole signal bit for
+ * bit, whichever slot it sits in, whatever the other rows carry and however many calls it sits out.  Two launches (one when no row emits,
+ * none for L == 0 without finish).
+ * AC_EINVAL for a null or misaligned state, geometry that is not a filter bank's, n_rows outside [1, B], a slot outside [0, B) or listed
+ * twice, a negative or overflowing count, a negative L, a null list, or a pitch shorter than its row (y_pitch: than the longest m_r);
+ * AC_ENOMEM for a short state or y_capacity below the longest m_r.  After a refusal the state is as it was; nothing allocates or
+ * synchronises. */
+int ac_resample_stream_reset_slots(void* state_dev, size_t state_bytes, int B, int n, int o, int taps, int width, const int* slots_host,
+                                   const int* slots_dev, int n_rows, void* stream);
+int ac_resample_stream_push_slots(void* state_dev, size_t state_bytes, int B, const int* slots_host, const long long* consumed_host,
+                                  const int* slots_dev, const long long* consumed_dev, int n_rows, const float* x_dev, long long x_pitch,
+                                  int L, const float* kern_dev, int n, int o, int taps, int width, float* y_dev, long long y_pitch,
+                                  long long y_capacity, int finish, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */

@@ -6,6 +6,7 @@ seeded synthetic weights, noise input / random tokens.
     python tools/encodec_stream_latency.py --sweep [--out profiles/encodec_stream_latency.json]
     python tools/encodec_stream_latency.py --sweep --sample-rate 16000 --out profiles/encodec_stream_latency_16k.json
     python tools/encodec_stream_latency.py --sessions --out profiles/encodec_sessions_latency.json
+    python tools/encodec_stream_latency.py --sessions --sample-rate 16000 --out profiles/encodec_sessions_latency_16k.json
 
 Same method as tools/mimi_stream_latency.py: after the stream's own start-up hold (one push of WARMUP_FRAMES frames, not timed) and
 `--warmup` untimed pushes, every push is timed on the host from `push` to a stream synchronisation (what a caller waiting for its
@@ -26,7 +27,13 @@ n = 1 / 8 / 64 listed slots against the lockstep stream of batch n, one-frame pu
 on ALTERNATING pushes (pool, stream, pool, ...), so that clock and cache state are shared; after each one's start-up release and
 `--warmup` untimed pushes, `--pushes` pushes of each are timed as above.  "mixed tick" is the pool's push in which one listed slot
 releases its 7 held frames beside n - 1 steady slots (two native calls; the slot is closed, reopened and fed 6 frames, untimed, before
-every timed push).  Nothing is gated on these numbers: the lockstep stream at the same n is the baseline of a subset push."""
+every timed push).  Nothing is gated on these numbers: the lockstep stream at the same n is the baseline of a subset push.
+
+`--sessions --sample-rate R` (R != 24000) also times the resampling pool (`encode_sessions / decode_sessions(64, resample=True)` of a
+codec built for rate R) against the plain 24 kHz pool at the same n, again on alternating pushes in one process.
+The pushes cover the same audio time, one frame: at 16 kHz an encode push is 213 or 214 samples, of which the resampler completes 318
+to 321, so a push of the resampling pool runs one frame most of the time and none or two now and then, as a caller's would.  The
+difference of the two medians is what the per-slot resampler costs per push (one host-to-device copy and two launches)."""
 import argparse
 import json
 import os
@@ -155,6 +162,42 @@ def measure_sessions(codec, direction, n, pushes, warmup, capacity=64):
             "launches_one_pool_push": int(sum(k for _, k, _, _, _ in stats)), "kernel_ms_one_pool_push": round(sum(ms for _, _, ms, _, _ in stats), 4)}
 
 
+def measure_sessions_resampled(codec, codec_r, direction, n, pushes, warmup, capacity=64):
+    """The resampling pool of `codec_r` (the caller's rate) against the plain pool of `codec` at the same n, alternating."""
+    cfg = codec.config
+    hop, K, rate = cfg.hop_length, codec.num_codebooks, int(codec_r.sample_rate)
+    enc = direction == "encode"
+    pools = {"plain": codec.encode_sessions(capacity) if enc else codec.decode_sessions(capacity),
+             "resampling": codec_r.encode_sessions(capacity, resample=True) if enc else codec_r.decode_sessions(capacity, resample=True)}
+    W = pools["plain"].WARMUP_FRAMES + 1            # (one frame more: the resampler holds the last 0.5 ms back)
+    slots = {who: [p.open() for _ in range(capacity)][:: capacity // n][:n] for who, p in pools.items()}
+    frames = W + warmup + pushes
+    if enc:
+        at = {"plain": lambda a: a * hop, "resampling": lambda a: (a * hop * rate + cfg.sampling_rate // 2) // cfg.sampling_rate}
+        data = {who: torch.from_numpy((prng.normal(14, "sessions_latency", (n, at[who](frames))) * 0.1).astype(np.float32)).cuda() for who in pools}
+        piece = lambda who, a, m: data[who][:, at[who](a):at[who](a + m)]      # noqa: E731
+    else:
+        toks = torch.from_numpy(prng.randint(14, "sessions_latency", (n, frames, K), cfg.codebook_size)).to(torch.int64).cuda()
+        piece = lambda who, a, m: toks[:, a:a + m]                # noqa: E731
+    for who, p in pools.items():
+        assert all(r.shape[0] > 0 for r in p.push(slots[who], piece(who, 0, W)))      # the start-up hold, released as one push
+    torch.cuda.synchronize()
+    lat = {who: [] for who in pools}
+    for i in range(warmup + pushes):
+        for who, p in pools.items():
+            x = piece(who, W + i, 1)
+            t0 = time.perf_counter()
+            p.push(slots[who], x)
+            torch.cuda.synchronize()
+            if i >= warmup:
+                lat[who].append((time.perf_counter() - t0) * 1e3)
+    q = lambda v: (round(float(np.median(v)), 3), round(float(np.percentile(v, 99)), 3))      # noqa: E731
+    (pm, pp), (rm, rp) = q(lat["plain"]), q(lat["resampling"])
+    return {"direction": direction, "capacity": capacity, "listed": n, "frames_per_push": 1, "pushes": pushes, "warmup": warmup, "sample_rate": rate,
+            "plain_pool_median_ms": pm, "plain_pool_p99_ms": pp, "resampling_pool_median_ms": rm, "resampling_pool_p99_ms": rp,
+            "resampling_minus_plain_median_ms": round(rm - pm, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1)
@@ -183,6 +226,10 @@ def main():
                 rows.append(measure_sessions(codec, d, n, a.pushes, a.warmup))
                 rows[-1]["precision"] = a.precision or "default"
                 print(json.dumps(rows[-1]), flush=True)
+                if len(variants) > 1:
+                    rows.append(measure_sessions_resampled(codec, variants[1][0], d, n, a.pushes, a.warmup))
+                    rows[-1]["precision"] = a.precision or "default"
+                    print(json.dumps(rows[-1]), flush=True)
     for d, B, F in runs:
         for c, rs in variants:
             rows.append(measure(c, d, B, F, a.pushes, a.warmup, rs))
