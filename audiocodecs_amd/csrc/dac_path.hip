@@ -101,8 +101,10 @@ bool dac_unit_fused(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int 
     *rc_out = AC_OK;
     // (96 channels only: measured per unit, 32 clips -- 14.5 -> 13.9 ms; the 64-channel units LOSE, 6.9 -> 8.7 ms: their two-launch path runs
     //  64 x 32 wave tiles at three workgroups per CU, the wave-local second product needs 32 x 64 ones; profiles/r4_variants.md.
-    //  The developer switches that select a tap-GEMM code path -- slab reload per tap, staged epilogue -- mean the tap-GEMM.)
-    if (h->gemm_fp32 || h->dbg || h->dev.dac_unit == 0 || h->dev.tap_dil == 0 || h->dev.tap_epi_staged != 0 || C != 96 || ru.c7.N != C || ru.c1.N != C || ru.c1.Ktot != C || ru.c7.Ktot != 7 * C) return false;
+    //  The developer switches that select a tap-GEMM code path -- slab reload per tap, staged epilogue -- mean the tap-GEMM.
+    //  The test hook does not change the route: it wants each unit's OUTPUT only, dac_res_unit then asks for the raw flavour of
+    //  every unit (want_raw) and the kernel's epilogue writes it -- so the kernel the hook sees is the one that ships.)
+    if (h->gemm_fp32 || h->dev.dac_unit == 0 || h->dev.tap_dil == 0 || h->dev.tap_epi_staged != 0 || C != 96 || ru.c7.N != C || ru.c1.N != C || ru.c1.Ktot != C || ru.c7.Ktot != 7 * C) return false;
     if (!ru.c7.has_bias || !ru.c1.has_bias || !out.elu || !next.a || next.n < C) return false;
     auto w1 = h->w6_of.find(ru.c7.w_off), w2 = h->w6_of.find(ru.c1.w_off);
     auto i1 = h->winv_of.find(ru.c7.w_off), i2 = h->winv_of.find(ru.c1.w_off);

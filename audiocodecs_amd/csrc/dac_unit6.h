@@ -22,7 +22,8 @@
 // Wider units (128 .. 1536 channels) keep two launches: their rows span several waves, the second product would need every wave's
 // share of the hidden activation -- the accumulators twice or 66 - 131 KB of LDS per 128-row tile (profiles/r4_variants.md).
 // The result differs from the two-launch path by the rounding of the hidden activation's lo plane (a different power-of-two
-// scale); both are fp32-grade (split16.h) and meet the same parity bar (tests/test_dac_gpu_parity.py, test_round4_kernels_gpu.py).
+// scale); both are fp32-grade (split16.h) and meet the same parity bar (tests/test_dac_gpu_parity.py, test_round4_kernels_gpu.py),
+// and each is held to fp64 on its own, per unit, under the capture hook (tests/test_layer_isolation_gpu.py).
 #pragma once
 #include "tap_gemm6.h"
 

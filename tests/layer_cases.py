@@ -10,8 +10,14 @@ GPU's own previous output.  No GPU needed: tests/test_layer_cases.py checks the 
 Layouts: the capture writes every tensor as [B][L][C].  "BCL" taps are [B,C,L] in the oracle (convs, LSTM, norms of the
 vocoder backbone); "BTH" taps are [B,T,H] in the oracle too (Mimi's transformer layers: the capture's own layout).
 
-What the capture does not emit is not in these lists: the last conv of EnCodec's and WavTokenizer's encoder, and the last
-conv (head) of every decoder, leave through the call's result, not through the hook."""
+`taps_of` lists what the capture emits, in order.  Six (codec, direction) pairs end in a layer that the capture does not emit
+because it leaves through the call's RESULT: the last conv of EnCodec's and WavTokenizer's encoder (`sig_to_feats`) and the head
+of every decoder (`toks_to_sig`).  `result_tap_of` names that layer -- a `Tap` with `result=True`: its oracle layer, the tap it
+reads, and the layout of the call's return value -- and `layer_fns` holds its function too, so that a test can run it, like any
+other layer, on the GPU's own last tap and compare with what the call returned.  Result layouts are those of the return value
+itself: "BND" features [B,N,D] (the oracle's [B,D,N] with its last two axes exchanged), "BT" waveforms [B,T] (the oracle's
+[B,1,T] without the channel axis; WavTokenizer's ISTFT head gives [B, N*hop] as it is).  DAC's and Mimi's encoders end in a
+captured tap (`encoder.conv2`, `downsample`): they have no result layer."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -30,6 +36,7 @@ class Tap:
     layout: str                  # "BCL" or "BTH"
     src: str                     # the tap this layer reads, or INPUT
     skip: Optional[str] = None   # reason: captured, but compared by no layer test (its size is that of INPUT)
+    result: bool = False         # not captured: the layer leaves through the call's return value; layout "BND" or "BT"
 
 
 def _chain(names, oracle_names, layout="BCL", first_src=INPUT) -> List[Tap]:
@@ -129,6 +136,32 @@ def mimi_taps(cfg, direction: str) -> List[Tap]:
     return [skip, up] + tf + _chain([_mimi_short(n) for n in o], o, "BCL", tf[-1].name)
 
 
+def _seanet_result(taps: List[Tap], direction: str) -> Tap:
+    """EnCodec / WavTokenizer encoder: the final conv two module indices after the LSTM (the ELU between them has no entry);
+    EnCodec decoder: the final conv two after the last residual block."""
+    last = taps[-1].name
+    name = f"{last[:3]}{int(last[3:]) + 2}"
+    return Tap(name, name, "BND" if direction == "encode" else "BT", last, result=True)
+
+
+def result_tap_of(codec: str, cfg, direction: str) -> Optional[Tap]:
+    """The layer that leaves through the call's result (`sig_to_feats` when encoding, `toks_to_sig` when decoding), or None where
+    the last layer of the direction is a captured tap.  It reads the LAST tap of `taps_of`."""
+    assert direction in ("encode", "decode")
+    taps = taps_of(codec, cfg, direction)
+    if codec == "encodec":
+        return _seanet_result(taps, direction)
+    if codec == "wavtokenizer":
+        return _seanet_result(taps, direction) if direction == "encode" else Tap("sig", "sig", "BT", taps[-1].name, result=True)
+    if direction == "encode":
+        return None
+    if codec == "dac":
+        return Tap("decoder.conv2", "decoder.conv2", "BT", taps[-1].name, result=True)
+    o = taps[-1].oracle                                    # Mimi: decoder.layers.{i}, the last block -> the head two after it
+    o = f"decoder.layers.{int(o.rsplit('.', 1)[1]) + 2}"
+    return Tap(_mimi_short(o), o, "BT", taps[-1].name, result=True)
+
+
 TAPS = {"encodec": encodec_taps, "wavtokenizer": wavtok_taps, "dac": dac_taps, "mimi": mimi_taps}
 
 
@@ -141,7 +174,8 @@ def taps_of(codec: str, cfg, direction: str) -> List[Tap]:
 def layer_fns(codec: str, cfg, W, direction: str) -> Dict[str, Callable]:
     """tap name -> fn(input tap's tensor, in the oracle layout of the INPUT tap) -> this tap's tensor in its own oracle
     layout, in the dtype of W.  Where a BTH layer reads a BCL tap or the reverse (Mimi: around the transformers) the
-    transpose is added here.  INPUT is [B,1,T] samples (encode) or [B,hidden,N] dequantised features (decode)."""
+    transpose is added here.  INPUT is [B,1,T] samples (encode) or [B,hidden,N] dequantised features (decode).
+    The result layer of `result_tap_of`, where there is one, comes last: its fn gives the call's return value, [B,N,D] or [B,T]."""
     if codec == "encodec":
         from oracle import encodec_oracle as O
         layers = dict(O.encoder_layers(cfg, W) if direction == "encode" else O.decoder_layers(cfg, W))
@@ -168,6 +202,16 @@ def layer_fns(codec: str, cfg, W, direction: str) -> Dict[str, Callable]:
         if layout[t.src] != t.layout:      # [B,C,L] <-> [B,T,H]
             fn = (lambda f: lambda x: f(x.transpose(1, 2)))(fn)
         out[t.name] = fn
+    r = result_tap_of(codec, cfg, direction)
+    if r is not None:
+        assert layout[r.src] == "BCL" and r.name not in out
+        fn = layers[r.oracle]
+        if r.layout == "BND":                 # [B,D,N] -> [B,N,D]
+            out[r.name] = (lambda f: lambda x: f(x).transpose(1, 2))(fn)
+        elif r.oracle == "sig":               # the ISTFT head gives [B, N*hop] itself
+            out[r.name] = fn
+        else:                                 # [B,1,T] -> [B,T]
+            out[r.name] = (lambda f: lambda x: f(x)[:, 0])(fn)
     return out
 
 

@@ -7,7 +7,10 @@ Mimi's `transformer_layers` / `downsample` / `upsample`) on the tiny fixtures:
     to -- reproduces the committed activations bit for bit in fp32.  Mimi's fixtures come from the reference's own modules, whose
     attention is another kernel than the oracle's restatement: from the first transformer layer on they agree to the 5e-6 of
     tests/test_mimi_oracle_golden.py, not to the bit (they did not before the layers became addressable either); everything
-    upstream of it, and every tap of the other three codecs, is bit-equal."""
+    upstream of it, and every tap of the other three codecs, is bit-equal;
+  * the six result layers (`result_tap_of`: the layers that leave through the call's return value, not through the hook) close
+    the lists: the tap functions folded from the input and then the result function give the oracle's own `sig_to_feats` /
+    `toks_to_sig`, to the bit, in the layout of the return value."""
 import numpy as np
 import pytest
 import torch
@@ -84,7 +87,9 @@ def test_layer_lists_reproduce_the_tiny_fixtures(codec, name, request):
     for direction, x in (("encode", x_enc), ("decode", x_dec)):
         taps = LC.taps_of(codec, cfg, direction)
         fns = LC.layer_fns(codec, cfg, W, direction)
-        assert [t.name for t in taps if not t.skip] == list(fns)
+        res = LC.result_tap_of(codec, cfg, direction)
+        assert [t.name for t in taps if not t.skip] + ([res.name] if res else []) == list(fns)
+        assert not any(t.result for t in taps)           # taps_of is what the capture emits: no result layer in it
         vals, size, exact = {LC.INPUT: x}, 0, True
         for t in taps:
             if t.skip:                                   # the quantiser's output: the decoder's input, captured but no layer
@@ -119,6 +124,49 @@ def test_layer_lists_reproduce_the_tiny_fixtures(codec, name, request):
             assert np.array_equal(back[t.name], vals[t.name].numpy()), t.name
         with pytest.raises(AssertionError):
             LC.split_capture(flat[:-1], taps, lambda t: vals[t.name].shape)
+
+
+RESULTS = [("encodec", "encode", "enc15", "enc13"), ("encodec", "decode", "dec15", "dec13"), ("wavtokenizer", "encode", "enc15", "enc13"),
+           ("wavtokenizer", "decode", "sig", "final"), ("dac", "decode", "decoder.conv2", None), ("mimi", "decode", "decoder.layers.14", None)]
+
+
+@pytest.mark.parametrize("name", ["tiny_taps", "tiny_odd"])
+@pytest.mark.parametrize("codec,direction,full_oracle,full_src", RESULTS, ids=[f"{c}-{d}" for c, d, _, _ in RESULTS])
+def test_result_layers_close_the_lists(codec, direction, full_oracle, full_src, name, request):
+    """Taps folded from the input, then the result layer == the oracle's own entry point, bit for bit; and the names at the
+    full-size configs are the ones the oracles' lists end with."""
+    import importlib
+
+    name = "tiny_ragged" if codec == "encodec" and name == "tiny_odd" else name
+    cfg, W, z, meta, x_enc, x_dec = _setup(codec, name, request)
+    torch.set_num_threads(min(8, torch.get_num_threads()))
+    O = importlib.import_module({"encodec": "oracle.encodec_oracle", "mimi": "oracle.mimi_oracle", "dac": "oracle.dac_oracle",
+                                 "wavtokenizer": "oracle.wavtokenizer_oracle"}[codec])
+    taps, fns = LC.taps_of(codec, cfg, direction), LC.layer_fns(codec, cfg, W, direction)
+    res = LC.result_tap_of(codec, cfg, direction)
+    assert res is not None and res.result and not res.skip and res.src == taps[-1].name and list(fns)[-1] == res.name
+    vals = {LC.INPUT: x_enc if direction == "encode" else x_dec}
+    with torch.no_grad():
+        for t in taps:
+            vals[t.name] = vals[LC.INPUT] if t.skip else fns[t.name](vals[t.src])
+        got = fns[res.name](vals[res.src])
+        if direction == "encode":
+            want = O.sig_to_feats(cfg, W, x_enc[:, 0])
+            assert res.layout == "BND" and want.shape == (x_enc.shape[0], vals[res.src].shape[2], want.shape[2])
+        else:
+            want = O.toks_to_sig(cfg, W, torch.from_numpy(z[f"{name}.toks"].astype(np.int64)))
+            assert res.layout == "BT" and want.dim() == 2
+    assert got.dtype == torch.float32 and got.shape == want.shape
+    assert torch.equal(got, want), float((got - want).abs().max())
+    # the full-size configs: the names the oracles' lists end with
+    fx = {"encodec": "checkpoints", "mimi": "mimi_checkpoints", "dac": "dac_checkpoints", "wavtokenizer": "wavtok_checkpoints"}[codec]
+    full = request.getfixturevalue(fx)("full", 0)[0]
+    rf = LC.result_tap_of(codec, full, direction)
+    assert rf.oracle == full_oracle and rf.src == LC.taps_of(codec, full, direction)[-1].name
+    if full_src:
+        assert rf.src == full_src
+    if codec in ("dac", "mimi"):      # their encoders end in a captured tap
+        assert LC.result_tap_of(codec, cfg, "encode") is None and LC.result_tap_of(codec, full, "encode") is None
 
 
 def test_mimi_transformer_layer_offset_and_names(mimi_checkpoints):
