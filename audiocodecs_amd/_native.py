@@ -12,7 +12,7 @@ import os
 
 import torch  # noqa: F401  (loads libamdhip64 first)
 
-__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
+__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
            "Handle", "HandleOwner"]
 
 AC_MAX_RATIOS = 8
@@ -117,6 +117,23 @@ class AcWavtokConfig(C.Structure):
     ]
 
 
+class AcVocosConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("input_channels", C.c_int32),
+        ("codebook_size", C.c_int32),
+        ("max_codebooks", C.c_int32),
+        ("backbone_dim", C.c_int32),
+        ("intermediate_dim", C.c_int32),
+        ("num_layers", C.c_int32),
+        ("adanorm_num_embeddings", C.c_int32),
+        ("n_fft", C.c_int32),
+        ("hop_length", C.c_int32),
+        ("bandwidth_id", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class AcKernelStat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 96),
@@ -135,6 +152,7 @@ EXPORTS = {
     "ac_mimi_create": (_i, [C.POINTER(AcMimiConfig), C.POINTER(_vp)]),
     "ac_dac_create": (_i, [C.POINTER(AcDacConfig), C.POINTER(_vp)]),
     "ac_wavtok_create": (_i, [C.POINTER(AcWavtokConfig), C.POINTER(_vp)]),
+    "ac_vocos_create": (_i, [C.POINTER(AcVocosConfig), C.POINTER(_vp)]),
     "ac_decode_feats": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "ac_load_weights": (_i, [_vp, C.c_char_p, _vp, _sz]),
     "ac_set_precision": (_i, [_vp, _i]),
@@ -360,12 +378,22 @@ class HandleOwner:
     # ---- measurement hook used by bench.py ------------------------------------------------------
     def profile_kernels(self, fn):
         """Run fn() with per-kernel HIP-event timing armed; returns [(name, launches, ms, flops, bytes)]."""
-        nat = self._any_native()
-        check(nat.lib.ac_profile_begin(nat.h), nat.h, "ac_profile_begin")
+        nats = self._profiled_handles()
+        for nat in nats:
+            check(nat.lib.ac_profile_begin(nat.h), nat.h, "ac_profile_begin")
         try:
             fn()
         finally:
-            buf = (AcKernelStat * 256)()
-            n = nat.lib.ac_profile_end(nat.h, buf, 256)
-        check(n, nat.h, "ac_profile_end")
-        return [(buf[i].name.decode(), buf[i].launches, buf[i].total_ms, buf[i].flops, buf[i].bytes) for i in range(n)]
+            ends = []
+            for nat in nats:
+                buf = (AcKernelStat * 256)()
+                ends.append((nat, buf, nat.lib.ac_profile_end(nat.h, buf, 256)))
+        out = []
+        for nat, buf, n in ends:
+            check(n, nat.h, "ac_profile_end")
+            out += [(buf[i].name.decode(), buf[i].launches, buf[i].total_ms, buf[i].flops, buf[i].bytes) for i in range(n)]
+        return out
+
+    def _profiled_handles(self):
+        """The handles `profile_kernels` arms: the wrapper's handle (a wrapper with a second handle map adds what exists of it)."""
+        return [self._any_native()]

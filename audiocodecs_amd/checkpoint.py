@@ -27,7 +27,7 @@ import torch
 from . import prng
 from .config import EncodecConfig
 
-__all__ = ["conv_specs", "synthetic_state_dict", "fold_weight_norm", "mimi_conv_specs", "synthetic_mimi_state_dict", "mimi_codebook", "dac_conv_specs", "dac_snake_specs", "synthetic_dac_state_dict", "wavtok_encoder_specs", "wavtok_lstm_prefix", "synthetic_wavtok_state_dict"]
+__all__ = ["conv_specs", "synthetic_state_dict", "fold_weight_norm", "mimi_conv_specs", "synthetic_mimi_state_dict", "mimi_codebook", "dac_conv_specs", "dac_snake_specs", "synthetic_dac_state_dict", "wavtok_encoder_specs", "wavtok_lstm_prefix", "synthetic_wavtok_state_dict", "synthetic_vocos_state_dict"]
 
 CODEBOOK_S0 = 0.10
 CODEBOOK_RHO = 0.94
@@ -387,6 +387,12 @@ def synthetic_wavtok_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
     sd[f"{q}.cluster_size"] = torch.ones(cfg.codebook_size)
     sd[f"{q}.inited"] = torch.tensor([1.0])
 
+    _vocos_backbone_and_head(sd, cfg, seed, cfg.dimension, pos_net=True)
+    return sd
+
+
+def _vocos_backbone_and_head(sd, cfg, seed: int, in_channels: int, pos_net: bool) -> None:
+    """VocosBackbone (with WavTokenizer's pos_net or, Vocos-for-EnCodec, without) and ISTFTHead into `sd`; every draw is keyed by its name."""
     C, I = cfg.backbone_dim, cfg.intermediate_dim
 
     def conv(prefix, cin, cout, k, gain=1.0):
@@ -401,19 +407,20 @@ def synthetic_wavtok_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
         sd[f"{prefix}.scale.weight"] = _f32(prng.uniform(seed, prefix + ".s", (cfg.adanorm_num_embeddings, C), 0.8, 1.2))
         sd[f"{prefix}.shift.weight"] = _f32(prng.normal(seed, prefix + ".h", (cfg.adanorm_num_embeddings, C)) * 0.05)
 
-    conv("backbone.embed", cfg.dimension, C, 7)
-    for i in (0, 1, 3, 4):     # ResnetBlocks of pos_net
+    conv("backbone.embed", in_channels, C, 7)
+    for i in (0, 1, 3, 4) if pos_net else ():     # ResnetBlocks of pos_net
         pp = f"backbone.pos_net.{i}"
         norm(f"{pp}.norm1", C)
         conv(f"{pp}.conv1", C, C, 3)
         norm(f"{pp}.norm2", C)
         conv(f"{pp}.conv2", C, C, 3, gain=0.5)
-    pa = "backbone.pos_net.2"  # AttnBlock
-    norm(f"{pa}.norm", C)
-    for nm in ("q", "k", "v"):
-        conv(f"{pa}.{nm}", C, C, 1, gain=2.0 if nm != "v" else 1.0)   # q, k gain: scores spread enough for a non-flat softmax
-    conv(f"{pa}.proj_out", C, C, 1, gain=0.5)
-    norm("backbone.pos_net.5", C)
+    if pos_net:
+        pa = "backbone.pos_net.2"  # AttnBlock
+        norm(f"{pa}.norm", C)
+        for nm in ("q", "k", "v"):
+            conv(f"{pa}.{nm}", C, C, 1, gain=2.0 if nm != "v" else 1.0)   # q, k gain: scores spread enough for a non-flat softmax
+        conv(f"{pa}.proj_out", C, C, 1, gain=0.5)
+        norm("backbone.pos_net.5", C)
     adanorm("backbone.norm")
     for l in range(cfg.num_layers):
         pl = f"backbone.convnext.{l}"
@@ -431,4 +438,20 @@ def synthetic_wavtok_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
     # head.istft.window: torch.hann_window(n_fft) (periodic) -- a registered buffer of the upstream module
     n = np.arange(cfg.n_fft, dtype=np.float64)
     sd["head.istft.window"] = _f32(0.5 - 0.5 * np.cos(2.0 * np.pi * n / cfg.n_fft))
+
+
+VOCOS_TABLE_S0 = 0.9
+VOCOS_TABLE_RHO = 0.7
+
+
+def synthetic_vocos_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A seeded state dict in the key layout of the published Vocos-for-EnCodec checkpoint (config.VocosConfig): the stacked code
+    tables on a shrinking per-stage scale (residual stages carry less and less), backbone and head exactly on
+    `synthetic_wavtok_state_dict`'s scales (the same draws by name).  The AdaLayerNorm rows differ, so a wrong bandwidth row shows."""
+    sd: Dict[str, torch.Tensor] = {}
+    name = "feature_extractor.codebook_weights"
+    t = prng.normal(seed, name, (cfg.max_codebooks, cfg.codebook_size, cfg.input_channels))
+    t = t * (VOCOS_TABLE_S0 * VOCOS_TABLE_RHO ** np.arange(cfg.max_codebooks))[:, None, None]
+    sd[name] = _f32(t.reshape(cfg.max_codebooks * cfg.codebook_size, cfg.input_channels))
+    _vocos_backbone_and_head(sd, cfg, seed, cfg.input_channels, pos_net=False)
     return sd

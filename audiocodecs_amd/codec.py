@@ -62,15 +62,21 @@ class Codec(torch.nn.Module, ABC):
         # codec.py:64-65: length defaults to ones(B) -- the "no padding" case
         return None if self._accepts_none_length else torch.ones(len(x), device=x.device)
 
+    def _handles(self):
+        """Every live native handle of this wrapper (a wrapper with a second handle map -- Encodec's Vocos decoder -- adds it)."""
+        return list(getattr(self, "_natives", {}).values())
+
     def _polled(self, out):
-        """strict mode: surface device-side failures of the call that just ran (ac_poll_status synchronises the stream)."""
+        """strict mode: surface device-side failures of the call that just ran (ac_poll_status synchronises the stream).  Every handle
+        of the wrapper on the result's device is polled: the one that produced the result is among them."""
         first = out[0] if isinstance(out, (tuple, list)) and out else out      # (a wrapper method may return several tensors)
         if self.strict and isinstance(first, torch.Tensor) and first.is_cuda:
-            out_dev = first.device
-            nat = getattr(self, "_natives", {}).get(out_dev.index)
-            if nat is not None:
-                from . import _native
+            from . import _native
 
+            out_dev = first.device
+            for nat in self._handles():
+                if nat.device.index != out_dev.index:
+                    continue
                 with torch.cuda.device(out_dev):
                     stream = torch.cuda.current_stream().cuda_stream
                     _native.check(nat.lib.ac_poll_status(nat.h, stream), nat.h, "ac_poll_status")
@@ -85,6 +91,10 @@ class Codec(torch.nn.Module, ABC):
     _graph_capable = True
     GRAPH_CACHE = 8               # graphs (each with a private workspace and static tensors) a codec keeps
 
+    def _graph_ok(self, name) -> bool:
+        """Whether call `name` ("sig_to_toks" / "toks_to_sig") may be replayed: per wrapper, or per call where a wrapper's calls differ."""
+        return self._graph_capable
+
     def _graphed(self, name, fn, x, length):
         """fn(x, None) through a hipGraph captured once per (call, shape, dtype, device).  The first call of a key runs
         eagerly (creates the handle, sizes the workspace) and then captures a second run into static input / output tensors; later calls
@@ -92,7 +102,7 @@ class Codec(torch.nn.Module, ABC):
         the library is capturable (no allocation, no synchronisation inside: include/audiocodecs_amd.h).  Results are bit-identical to the
         eager call's (tests/test_graph_mode_gpu.py)."""
         # (a caller-provided `length` is checked on the host by some wrappers -- encodec.py:84-89's mask size -- which a capture cannot do: eager)
-        if not (self.graph and self._graph_capable and isinstance(x, torch.Tensor) and x.is_cuda and x.shape[0] > 0 and length is None):
+        if not (self.graph and self._graph_ok(name) and isinstance(x, torch.Tensor) and x.is_cuda and x.shape[0] > 0 and length is None):
             return fn(x, length)
         key = (name, tuple(x.shape), x.dtype, x.device.index)
         ent = self._graphs.get(key)
@@ -117,7 +127,7 @@ class Codec(torch.nn.Module, ABC):
             # The graph bakes in the address of the workspace it was captured with, and the wrapper's own workspace tensor is REPLACED when a
             # later call needs a larger one: every graph gets a workspace of its own (allocated inside the capture, from the graph's private
             # pool, and kept alive with the graph), the wrapper's is put back afterwards.
-            nats = list(getattr(self, "_natives", {}).values())
+            nats = self._handles()
             kept = [n.ws for n in nats]
             for n in nats:
                 n.ws = None

@@ -12,7 +12,7 @@ import math
 from dataclasses import dataclass, field
 from typing import Tuple
 
-__all__ = ["EncodecConfig", "TINY", "ENCODEC_24KHZ", "MimiConfig", "MIMI_24KHZ", "MIMI_TINY", "DacConfig", "DAC_44KHZ", "DAC_24KHZ", "DAC_16KHZ", "DAC_TINY", "WavTokenizerConfig", "WAVTOK_40", "WAVTOK_75", "WAVTOK_TINY"]
+__all__ = ["EncodecConfig", "TINY", "ENCODEC_24KHZ", "MimiConfig", "MIMI_24KHZ", "MIMI_TINY", "DacConfig", "DAC_44KHZ", "DAC_24KHZ", "DAC_16KHZ", "DAC_TINY", "WavTokenizerConfig", "WAVTOK_40", "WAVTOK_75", "WAVTOK_TINY", "VocosConfig", "VOCOS_ENCODEC_24KHZ", "VOCOS_TINY"]
 
 
 @dataclass(frozen=True)
@@ -217,3 +217,27 @@ WAVTOK_75 = WavTokenizerConfig(ratios=(8, 5, 4, 2), n_fft=1280)          # ...fr
 # 1/8 width, hop 48: every activation fits a fixture
 WAVTOK_TINY = WavTokenizerConfig(num_filters=4, dimension=32, ratios=(4, 3, 2, 2), codebook_size=128, backbone_dim=256,
                                  intermediate_dim=512, num_layers=2, num_groups=32, n_fft=192)
+
+
+@dataclass(frozen=True)
+class VocosConfig:
+    """Architecture of the Vocos decoder the reference's `Encodec(use_vocos=True)` loads (/root/reference/audiocodecs/encodec.py:53-66:
+    `Vocos.from_pretrained("charactr/vocos-encodec-24khz")` of the package `vocos` -- NOT on disk; field values restate the published
+    config.yaml of that checkpoint: PARITY UNPINNED).  `codes_to_features` sums one row of each of the first K stacked code tables ->
+    Vocos backbone (k7 embed conv, AdaLayerNorm over 4 bandwidths, ConvNeXt blocks, LayerNorm; no pos_net) -> iSTFT head ("same" padding)."""
+
+    input_channels: int = 128          # width of a code vector == EnCodec's hidden_size
+    codebook_size: int = 1024
+    max_codebooks: int = 16            # tables stacked in feature_extractor.codebook_weights
+    backbone_dim: int = 384
+    intermediate_dim: int = 1152
+    num_layers: int = 8
+    adanorm_num_embeddings: int = 4
+    n_fft: int = 1280
+    hop_length: int = 320
+    bandwidths: Tuple[float, ...] = (1.5, 3.0, 6.0, 12.0)   # AdaLayerNorm row = index of the codec's bandwidth (encodec.py:56)
+
+
+VOCOS_ENCODEC_24KHZ = VocosConfig()
+# for TINY EnCodec (code vectors of width 16, hop 320); the backbone is WAVTOK_TINY's
+VOCOS_TINY = VocosConfig(input_channels=16, backbone_dim=256, intermediate_dim=512, num_layers=2)

@@ -1,5 +1,5 @@
 // C ABI of the MI355X codec paths (include/audiocodecs_amd.h): the extern "C" entry points.  The machinery behind them is in
-// core.hip (shared + EnCodec) and mimi_path.hip / dac_path.hip / wavtok_path.hip (one codec each, with its ac_*_create); core.h
+// core.hip (shared + EnCodec) and mimi_path.hip / dac_path.hip / wavtok_path.hip (one codec each, with its ac_*_create -- ac_vocos_create beside ac_wavtok_create); core.h
 // has the map.  gfx950 only.
 #include "core.h"
 #include "tap_route.h"
@@ -171,7 +171,9 @@ int ac_finalize(ac_handle* h) {
         if (kv.first.compare(0, 8, "encoder.") == 0) h->has_enc = true;
         if (kv.first.compare(0, 8, "decoder.") == 0) h->has_dec = true;
     }
-    if (!h->has_enc && !h->has_dec) return fail(h, AC_ESTATE, "no encoder.* or decoder.* tensor was loaded");
+    bool has_q = false;      // quantizer only: what Encodec(use_vocos=True, mode="decode") keeps (encodec.py:66) -- ac_embs and ac_dequantize
+    for (const auto& kv : h->host) has_q = has_q || kv.first.compare(0, 10, "quantizer.") == 0;
+    if (!h->has_enc && !h->has_dec && !has_q) return fail(h, AC_ESTATE, "no encoder.*, decoder.* or quantizer.* tensor was loaded");
     bool ok = true;
     h->enc_rb.resize(c.num_ratios);
     h->enc_down.resize(c.num_ratios);
@@ -359,6 +361,7 @@ int ac_quantize_ws(ac_handle* h, const float* feats, int B, int N, int K, int64_
     int rc = check_ready(h);
     if (rc) return rc;
     if (!feats || !toks || B < 1 || N < 1 || K < 1 || K > num_q(h)) return fail(h, AC_EINVAL, "ac_quantize: bad argument");
+    if (h->wt.vocos) return fail(h, AC_ESTATE, "ac_quantize: a Vocos handle decodes only (its tables are not a quantizer)");
     pool_bind(h, nullptr, 0, 0);      // (EnCodec / DAC: the codebook search runs outside split-operand arithmetic)
     if (h->arch == ARCH_DAC) return dac_vq_encode(h, (hipStream_t)stream, feats, B * N, K, reinterpret_cast<long long*>(toks), nullptr);
     if (h->arch == ARCH_MIMI) {

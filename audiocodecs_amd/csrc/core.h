@@ -132,6 +132,9 @@ struct WavtokPlan {
     size_t w2 = 0;                            // squared window [nfft]
     std::vector<WtCnxPlan> cnx;
     int bins = 0, npad = 0, hop_pad = 0, taps = 0;
+    // ac_vocos_create (Vocos-for-EnCodec): no encoder, no pos_net, `tables` stacked code tables [tables][codebook_size][dimension]
+    bool vocos = false;
+    int tables = 1;
 };
 
 struct ProfRec {

@@ -36,10 +36,11 @@ int wavtok_finalize(ac_handle* h, Packer& pk) {
     const int C = c.backbone_dim, I = c.intermediate_dim, D = c.dimension, hop = h->hop, nfft = c.n_fft;
     h->has_enc = h->has_dec = false;
     for (const auto& kv : h->host) {
-        if (kv.first.compare(0, 8, "encoder.") == 0) h->has_enc = true;
+        if (!m.vocos && kv.first.compare(0, 8, "encoder.") == 0) h->has_enc = true;   // (a Vocos handle decodes only: the EnCodec half upstream re-attaches is ignored)
         if (kv.first.compare(0, 9, "backbone.") == 0) h->has_dec = true;
     }
-    if (!h->has_enc && !h->has_dec) return fail(h, AC_ESTATE, "no feature_extractor.encodec.encoder.* or backbone.* tensor was loaded");
+    if (!h->has_enc && !h->has_dec)
+        return fail(h, AC_ESTATE, m.vocos ? "no backbone.* tensor was loaded" : "no feature_extractor.encodec.encoder.* or backbone.* tensor was loaded");
     // ---- encoder: the EnCodec plan over h->cfg (keys were mapped to the HF spelling by ac_load_weights)
     if (h->has_enc) {
         const ac_config& e = h->cfg;
@@ -55,8 +56,13 @@ int wavtok_finalize(ac_handle* h, Packer& pk) {
         ok = ok && pk.conv(a.enc_final, h->enc_final);
         if (!ok) return pk.rc;
     }
-    // ---- the codebook (both directions need it): plain, MFMA B-fragment order, squared norms
-    {
+    if (m.vocos) {   // ---- codes_to_features' stacked tables [tables * codebook_size][dimension] = rvq_decode_kernel's [K][C][H], as they are
+        const size_t n = (size_t)m.tables * c.codebook_size * D;
+        const std::vector<float>* e = pk.get("feature_extractor.codebook_weights", n);
+        if (!e) return pk.rc;
+        h->cb_plain = pk.reserve(n);
+        std::copy(e->begin(), e->end(), pk.blob.begin() + h->cb_plain);
+    } else {         // ---- the codebook (both directions need it): plain, MFMA B-fragment order, squared norms
         const int Cb = c.codebook_size;
         const std::vector<float>* e = pk.get("feature_extractor.encodec.quantizer.vq.layers.0._codebook.embed", (size_t)Cb * D);
         if (!e) return pk.rc;
@@ -82,7 +88,7 @@ int wavtok_finalize(ac_handle* h, Packer& pk) {
     // ---- backbone
     bool ok = pk.conv(ConvSpec{"backbone.embed", 0, D, C, 7, 1}, m.embed);
     const int rn_idx[4] = {0, 1, 3, 4};
-    for (int i = 0; ok && i < 4; ++i) {
+    for (int i = 0; ok && !m.vocos && i < 4; ++i) {
         const std::string p = "backbone.pos_net." + std::to_string(rn_idx[i]);
         ok = ok && wt_vec(pk, p + ".norm1.weight", C, m.rn[i].n1w) && wt_vec(pk, p + ".norm1.bias", C, m.rn[i].n1b);
         ok = ok && pk.conv(ConvSpec{p + ".conv1", 0, C, C, 3, 1}, m.rn[i].c1);
@@ -90,7 +96,7 @@ int wavtok_finalize(ac_handle* h, Packer& pk) {
         ok = ok && pk.conv(ConvSpec{p + ".conv2", 0, C, C, 3, 1}, m.rn[i].c2);
     }
     if (!ok) return pk.rc;
-    {   // q | k | v as one [3C][C] matrix
+    if (!m.vocos) {   // q | k | v as one [3C][C] matrix
         const std::string p = "backbone.pos_net.2.";
         std::vector<float> w, b;
         for (const char* nm : {"q", "k", "v"}) {
@@ -105,8 +111,8 @@ int wavtok_finalize(ac_handle* h, Packer& pk) {
         ok = pk.conv(ConvSpec{p + "qkv", 0, C, 3 * C, 1, 1}, m.qkv);
         ok = ok && pk.conv(ConvSpec{p + "proj_out", 0, C, C, 1, 1}, m.proj);
         ok = ok && wt_vec(pk, p + "norm.weight", C, m.an_w) && wt_vec(pk, p + "norm.bias", C, m.an_b);
+        ok = ok && wt_vec(pk, "backbone.pos_net.5.weight", C, m.g5w) && wt_vec(pk, "backbone.pos_net.5.bias", C, m.g5b);
     }
-    ok = ok && wt_vec(pk, "backbone.pos_net.5.weight", C, m.g5w) && wt_vec(pk, "backbone.pos_net.5.bias", C, m.g5b);
     ok = ok && wt_vec(pk, "backbone.norm.scale.weight", C, m.nsc, c.bandwidth_id) && wt_vec(pk, "backbone.norm.shift.weight", C, m.nsh, c.bandwidth_id);
     m.cnx.resize(c.num_layers);
     for (int l = 0; ok && l < c.num_layers; ++l) {
@@ -224,22 +230,13 @@ int wt_groupnorm(ac_handle* h, hipStream_t st, const float* x, size_t w_off, siz
     return AC_OK;
 }
 
-// feats [B][N][dimension] -> sig [B][N*hop]
-int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, int N, float* sig, WsPtrs& ws) {
-    const ac_wavtok_config& c = h->wcfg;
+// pos_net (2 ResnetBlocks, AttnBlock, 2 ResnetBlocks, GroupNorm) on x [B][N][C] in place; its last GroupNorm leaves the result in t
+int wt_pos_net(ac_handle* h, hipStream_t st, float* x, float* t, float* u, float* v, float* stats, int B, int N) {
     const WavtokPlan& m = h->wt;
-    const int C = c.backbone_dim, I = c.intermediate_dim, D = c.dimension, hop = h->hop;
+    const int C = h->wcfg.backbone_dim;
     const long long rows = (long long)B * N;
-    float* stats = ws.lstm.c;
-    float* x = ws.take();
-    float* t = ws.take();
-    float* u = ws.take();
-    float* v = ws.take();
+    const Act xa{x, (long long)N * C, C, N, C};
     int rc;
-    Act fa{feats, (long long)N * D, D, N, D};
-    if ((rc = wt_conv(h, st, m.embed, fa, 7, 3, 3, x, B))) return rc;
-    Act xa{x, (long long)N * C, C, N, C};
-    capture(h, st, xa, B);
     auto resnet = [&](const WtResnetPlan& r) -> int {
         int e;
         // (the normalisation kernel's waves are too many and too short to report an amax -- 144 K flushes on 64 words; the convs
@@ -275,7 +272,29 @@ int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, 
         capture(h, st, xa, B);
     }
     if ((rc = resnet(m.rn[2])) || (rc = resnet(m.rn[3]))) return rc;
-    if ((rc = wt_groupnorm(h, st, x, m.g5w, m.g5b, stats, t, B, N, 0))) return rc;
+    return wt_groupnorm(h, st, x, m.g5w, m.g5b, stats, t, B, N, 0);
+}
+
+// feats [B][N][dimension] -> sig [B][N*hop]
+int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, int N, float* sig, WsPtrs& ws) {
+    const ac_wavtok_config& c = h->wcfg;
+    const WavtokPlan& m = h->wt;
+    const int C = c.backbone_dim, I = c.intermediate_dim, D = c.dimension, hop = h->hop;
+    const long long rows = (long long)B * N;
+    float* stats = ws.lstm.c;
+    float* x = ws.take();
+    float* t = ws.take();
+    float* u = ws.take();
+    float* v = ws.take();
+    int rc;
+    Act fa{feats, (long long)N * D, D, N, D};
+    Act xa{x, (long long)N * C, C, N, C};
+    // the embed conv's output: pos_net's input x, or (Vocos-for-EnCodec: no pos_net) the AdaLayerNorm's input t
+    if ((rc = wt_conv(h, st, m.embed, fa, 7, 3, 3, m.vocos ? t : x, B))) return rc;
+    if (!m.vocos) {
+        capture(h, st, xa, B);
+        if ((rc = wt_pos_net(h, st, x, t, u, v, stats, B, N))) return rc;
+    }
     capture(h, st, Act{t, (long long)N * C, C, N, C}, B);
     if ((rc = layernorm_fwd(h, st, t, m.nsc, m.nsh, x, rows, C, 1e-6f))) return rc;   // AdaLayerNorm: LN * scale[cond] + shift[cond]
     capture(h, st, xa, B);
@@ -361,7 +380,7 @@ Workspace wavtok_plan_ws(const ac_handle* h, int B, int T_in, int N_frames, bool
     if (enc) return plan_ws(h, B, T_in, N_frames, true);
     const ac_wavtok_config& c = h->wcfg;
     Workspace w;
-    const size_t widest = std::max<size_t>(std::max(3 * c.backbone_dim, c.intermediate_dim), std::max(h->wt.npad, c.dimension));
+    const size_t widest = std::max<size_t>(std::max((h->wt.vocos ? 1 : 3) * c.backbone_dim, c.intermediate_dim), std::max(h->wt.npad, c.dimension));
     w.act_floats = align_up((size_t)B * N_frames * widest, 64);
     w.c = align_up((size_t)B * c.num_groups * 2, 64);
     w.total_bytes = (NACT * w.act_floats + 2 * w.gin + 2 * w.hseq + w.c) * sizeof(float) + 256;
@@ -416,6 +435,53 @@ extern "C" int ac_wavtok_create(const ac_wavtok_config* cfg, ac_handle** out) {
     e.device = c.device;
     h->hop = hop;
     h->D = c.num_filters << c.num_ratios;
+    *out = h;
+    return AC_OK;
+}
+
+// Vocos-for-EnCodec (include/audiocodecs_amd.h ac_vocos_config): WavTokenizer's decoder without pos_net over K <= max_codebooks stacked
+// code tables.  A decode-only ARCH_WAVTOK handle: h->wcfg carries the backbone and the head, h->cfg what rvq_decode_fwd reads.
+extern "C" int ac_vocos_create(const ac_vocos_config* cfg, ac_handle** out) {
+    if (!cfg || !out) return AC_EINVAL;
+    *out = nullptr;
+    if (cfg->struct_size != (int32_t)sizeof(ac_vocos_config)) return AC_EINVAL;
+    const ac_vocos_config& c = *cfg;
+    const int hop = c.hop_length;
+    if (c.input_channels < 16 || c.input_channels % 16 || c.input_channels > 512 || c.codebook_size < 1 || c.max_codebooks < 1 || c.max_codebooks > 64 ||
+        c.backbone_dim < 64 || c.backbone_dim % 64 || c.backbone_dim > 4 * 64 * DWLN_MAXV || c.intermediate_dim < 64 || c.intermediate_dim % 64 ||
+        c.num_layers < 0 || c.adanorm_num_embeddings < 1 || c.bandwidth_id < 0 || c.bandwidth_id >= c.adanorm_num_embeddings || c.n_fft < 4 || c.n_fft % 2 || hop < 4)
+        return AC_EINVAL;
+    // the same inverse-STFT geometry ac_wavtok_create accepts
+    if (c.n_fft % hop || c.n_fft / hop > 8 || hop % 4 || ((c.n_fft - hop) / 2) % 4 || (c.n_fft - hop) % 2) return AC_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c.device || c.device < 0) return AC_ENODEV;
+    ac_handle* h = new (std::nothrow) ac_handle();
+    if (!h) return AC_ENOMEM;
+    h->arch = ARCH_WAVTOK;
+    h->wt.vocos = true;
+    h->wt.tables = c.max_codebooks;
+    ac_wavtok_config& w = h->wcfg;
+    w.struct_size = (int32_t)sizeof(ac_wavtok_config);
+    w.dimension = c.input_channels;
+    w.num_ratios = 1;
+    w.ratios[0] = hop;
+    w.codebook_size = c.codebook_size;
+    w.backbone_dim = c.backbone_dim;
+    w.intermediate_dim = c.intermediate_dim;
+    w.num_layers = c.num_layers;
+    w.adanorm_num_embeddings = c.adanorm_num_embeddings;
+    w.n_fft = c.n_fft;
+    w.bandwidth_id = c.bandwidth_id;
+    w.device = c.device;
+    ac_config& e = h->cfg;               // rvq_decode_fwd, the K range of ac_decode / ac_dequantize / ac_embs, ac_num_frames
+    e.struct_size = (int32_t)sizeof(ac_config);
+    e.hidden_size = c.input_channels;
+    e.num_ratios = 1;
+    e.upsampling_ratios[0] = hop;
+    e.codebook_size = c.codebook_size;
+    e.num_quantizers = c.max_codebooks;
+    e.device = c.device;
+    h->hop = hop;
     *out = h;
     return AC_OK;
 }

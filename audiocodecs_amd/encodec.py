@@ -16,7 +16,7 @@ import torch
 from . import _native, checkpoint
 from ._native import Handle, _ptr, _stream  # noqa: F401  (_ptr and _stream stay importable from here: the tests' raw-ABI cases do)
 from .codec import Codec
-from .config import ENCODEC_24KHZ, EncodecConfig
+from .config import ENCODEC_24KHZ, VOCOS_ENCODEC_24KHZ, EncodecConfig, VocosConfig
 from .sessions import SessionPool
 from .streams import LockstepStream, StreamBackend, stream_checks
 
@@ -32,6 +32,15 @@ def _handle(cfg: EncodecConfig, folded: Dict[str, torch.Tensor], device: torch.d
     for i, r in enumerate(cfg.upsampling_ratios):
         c.upsampling_ratios[i] = r
     return Handle("ac_create", c, "is a gfx950 GPU visible?", folded, device, precision)
+
+
+def _vocos_handle(cfg: VocosConfig, bandwidth_id: int, sd: Dict[str, torch.Tensor], device: torch.device, precision=None) -> Handle:
+    c = _native.AcVocosConfig()
+    for f in ("input_channels", "codebook_size", "max_codebooks", "backbone_dim", "intermediate_dim", "num_layers", "adanorm_num_embeddings",
+              "n_fft", "hop_length"):
+        setattr(c, f, getattr(cfg, f))
+    c.bandwidth_id = bandwidth_id
+    return Handle("ac_vocos_create", c, "is a gfx950 GPU visible?", sd, device, precision)
 
 
 class Encodec(_native.HandleOwner, Codec):
@@ -51,23 +60,29 @@ class Encodec(_native.HandleOwner, Codec):
         precision: Optional[str] = None,
         strict: bool = False,
         graph: bool = False,
+        vocos_state_dict: Optional[Dict[str, torch.Tensor]] = None,
+        vocos_config: VocosConfig = VOCOS_ENCODEC_24KHZ,
     ):
         """`state_dict`: an HF-format EncodecModel state dict (keys of SURVEY.md Appendix A.3, e.g.
         `safetensors.torch.load_file(model.safetensors)` of facebook/encodec_24khz, or
         `checkpoint.synthetic_state_dict(cfg, seed)`).  When omitted the pretrained checkpoint is
         fetched through huggingface_hub like the reference does (needs network or a warm cache).
         `precision`: None / "fp32" = fp32 fidelity on the fp16 matrix pipe (split16: the parity arithmetic, default);
-        "fp32_exact" = exact fp32 products (include/audiocodecs_amd.h ac_set_precision)."""
+        "fp32_exact" = exact fp32 products (include/audiocodecs_amd.h ac_set_precision).
+        `use_vocos=True` (encodec.py:53-66): in the decoding modes `toks_to_sig` runs the Vocos decoder instead of the SEANet one, whose
+        weights are then never packed or uploaded (`mode="encode"` keeps no Vocos at all, :67-69).  `vocos_state_dict`: the state dict of
+        charactr/vocos-encodec-24khz (`torch.load(pytorch_model.bin)`, or `checkpoint.synthetic_vocos_state_dict(vocos_config, seed)`);
+        when omitted it is fetched through huggingface_hub like the reference does.  PARITY UNPINNED: the reference's `vocos` package is
+        not on disk, the path is held to a restatement of the published Vocos 0.1.0 modules (tests/vocos_ref.py).
+        With Vocos, `graph=True` replays `toks_to_sig` (no LSTM on that path); `sig_to_toks` still runs eagerly."""
         super().__init__(sample_rate, orig_sample_rate, mode)
         self.strict = bool(strict)   # codec.py: poll the handle after every call
         self.graph = bool(graph)     # codec.py: replay one hipGraph per (call, shape)
         self.precision = _native.check_precision(precision)
-        if use_vocos:
-            raise NotImplementedError("the Vocos decoder variant (encodec.py:53-66) is outside the MI355X path")
         if config.sampling_rate != orig_sample_rate:
             raise ValueError(f"config.sampling_rate ({config.sampling_rate}) != orig_sample_rate ({orig_sample_rate})")
         self.num_codebooks = num_codebooks
-        self.use_vocos = use_vocos
+        self.use_vocos = bool(use_vocos)
         self.vocab_size = config.codebook_size
         self.config = config
         self.bandwidth = (num_codebooks * 75) / 100  # encodec.py:50
@@ -80,6 +95,18 @@ class Encodec(_native.HandleOwner, Codec):
         elif mode == "decode":
             self._folded = {k: v for k, v in self._folded.items() if not k.startswith("encoder.")}
         self._natives: Dict[int, Handle] = {}
+        # encodec.py:53-69: with use_vocos a decoding mode swaps the SEANet decoder for Vocos (the quantizer stays: embs, toks_to_qfeats)
+        self._vocos_sd = None
+        self._vocos_natives: Dict[int, Handle] = {}
+        self.vocos_config = vocos_config
+        if self.use_vocos and mode != "encode":
+            if vocos_config.hop_length != config.hop_length or vocos_config.input_channels != config.hidden_size or vocos_config.codebook_size != config.codebook_size:
+                raise ValueError("vocos_config does not fit config: hop_length, input_channels == hidden_size and codebook_size must agree")
+            if vocos_state_dict is None:
+                vocos_state_dict = self._fetch_pretrained_vocos(int(orig_sample_rate / 1000))
+            keep = ("feature_extractor.codebook_weights", "backbone.", "head.")     # (upstream re-attaches feature_extractor.encodec.* at load time)
+            self._vocos_sd = {k: v for k, v in vocos_state_dict.items() if k.startswith(keep)}
+            self._folded = {k: v for k, v in self._folded.items() if not k.startswith("decoder.")}
 
     @staticmethod
     def _fetch_pretrained(tag: int):
@@ -90,8 +117,37 @@ class Encodec(_native.HandleOwner, Codec):
             raise ImportError("`pip install huggingface_hub safetensors` to fetch pretrained EnCodec weights")
         return load_file(hf_hub_download(f"facebook/encodec_{tag}khz", "model.safetensors"))
 
+    @staticmethod
+    def _fetch_pretrained_vocos(tag: int):
+        try:
+            from huggingface_hub import hf_hub_download
+        except ImportError:
+            raise ImportError("`pip install huggingface_hub` to fetch pretrained Vocos weights")
+        return torch.load(hf_hub_download(f"charactr/vocos-encodec-{tag}khz", "pytorch_model.bin"), map_location="cpu")
+
     def _new_handle(self, device: torch.device) -> Handle:
         return _handle(self.config, self._folded, device, self.precision)
+
+    def _vocos_bandwidth_id(self) -> int:
+        """encodec.py:56: `[1.5, 3.0, 6.0, 12.0].index(self.bandwidth)` -- a ValueError at the call for any other `num_codebooks`."""
+        return list(self.vocos_config.bandwidths).index(self.bandwidth)
+
+    def _vocos_for(self, t: torch.Tensor, bandwidth_id: int) -> Handle:
+        if not t.is_cuda:
+            raise _native.NativeError("audiocodecs_amd runs on MI355X only: move the input to a cuda device (there is deliberately no CPU fallback)")
+        idx = t.device.index
+        if idx not in self._vocos_natives:
+            self._vocos_natives[idx] = _vocos_handle(self.vocos_config, bandwidth_id, self._vocos_sd, t.device, self.precision)
+        return self._vocos_natives[idx]
+
+    def _handles(self):
+        return list(self._natives.values()) + list(self._vocos_natives.values())
+
+    def _profiled_handles(self):
+        return [self._any_native()] + list(self._vocos_natives.values())
+
+    def _graph_ok(self, name) -> bool:
+        return name == "toks_to_sig" and self._vocos_sd is not None      # the Vocos decode has no LSTM: replayable
 
     def _num_quantizers(self) -> int:
         """[HF] modeling_encodec.py:564-567 rejects bandwidths outside config.target_bandwidths,
@@ -174,10 +230,14 @@ class Encodec(_native.HandleOwner, Codec):
     # override
     def _toks_to_sig(self, toks, length):
         # toks: [B, N, K] -> [B, N*hop]
+        vocos = self._vocos_sd is not None
+        bw_id = self._vocos_bandwidth_id() if vocos else None      # (raises before any device or shape check, like the reference)
         B, N, K = toks.shape
+        if vocos and not 1 <= K <= self.vocos_config.max_codebooks:
+            raise ValueError(f"Vocos decodes 1 to {self.vocos_config.max_codebooks} codebooks, the tokens have {K}")
         if B == 0:
             return torch.empty(0, N * self.config.hop_length, dtype=torch.float32, device=toks.device)
-        nat = self._native_for(toks)
+        nat = self._vocos_for(toks, bw_id) if vocos else self._native_for(toks)
         toks = toks.to(torch.int64).contiguous()
         sig = torch.empty(B, N * self.config.hop_length, dtype=torch.float32, device=toks.device)
         with torch.cuda.device(nat.device):

@@ -172,6 +172,33 @@ typedef struct ac_wavtok_config {
     int32_t device;
 } ac_wavtok_config;
 
+/* Vocos decoder for EnCodec tokens (the reference's Encodec(use_vocos=True), audiocodecs/encodec.py:53-66,130-138, loads
+ * charactr/vocos-encodec-24khz through the package `vocos`, which is NOT on disk: PARITY UNPINNED -- this path is pinned to a
+ * restatement of the published Vocos 0.1.0 modules, tests/vocos_ref.py over oracle/wavtokenizer_oracle.py).  Replaces
+ *     encodec.py:133-137   vocos.codes_to_features(toks) + vocos.decode(feats, bandwidth_id=...)   -> ac_decode
+ * A decode-only handle: WavTokenizer's decoder without pos_net.  ac_decode(toks [B,N,K]) sums rows toks[..,k] + k*codebook_size of
+ * "feature_extractor.codebook_weights" [max_codebooks*codebook_size, input_channels] for the K the CALL gives (1..max_codebooks),
+ * then "backbone.embed.*" (Conv1d k7), "backbone.norm.{scale,shift}.weight" (AdaLayerNorm, row bandwidth_id),
+ * "backbone.convnext.{l}.{dwconv,norm.scale,norm.shift,pwconv1,pwconv2}.*" + "...gamma", "backbone.final_layer_norm.*",
+ * "head.out.*" and the inverse STFT ("same" padding; optional "head.istft.window", periodic Hann when absent).  Every other key is
+ * ignored.  Serves ac_load_weights, ac_set_precision, ac_finalize, ac_decode_workspace_bytes, ac_decode, ac_dequantize (the
+ * summed features), ac_embs (the tables), ac_poll_status, ac_debug_capture, ac_profile_*, ac_hop_length, ac_destroy; the
+ * encode-side calls fail ("without encoder weights"). */
+typedef struct ac_vocos_config {
+    int32_t struct_size;               /* = sizeof(ac_vocos_config)                                           */
+    int32_t input_channels;            /* 128: width of a code vector == EnCodec's hidden_size                */
+    int32_t codebook_size;             /* 1024                                                                */
+    int32_t max_codebooks;             /* 16 tables in codebook_weights                                       */
+    int32_t backbone_dim;              /* 384 (a multiple of 64, at most 1024)                                */
+    int32_t intermediate_dim;          /* 1152                                                                */
+    int32_t num_layers;                /* 8 ConvNeXt blocks                                                   */
+    int32_t adanorm_num_embeddings;    /* 4: bandwidths 1.5, 3, 6, 12 kbps                                    */
+    int32_t n_fft;                     /* 1280; a multiple of hop_length                                      */
+    int32_t hop_length;                /* 320                                                                 */
+    int32_t bandwidth_id;              /* the AdaLayerNorm row: [1.5, 3.0, 6.0, 12.0].index(bandwidth)        */
+    int32_t device;
+} ac_vocos_config;
+
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int ac_version(void);
 
@@ -188,6 +215,9 @@ int ac_dac_create(const ac_dac_config* cfg, ac_handle** out);
 
 /* Same, for a WavTokenizer handle. */
 int ac_wavtok_create(const ac_wavtok_config* cfg, ac_handle** out);
+
+/* Same, for a Vocos-for-EnCodec decoder handle (decode only). */
+int ac_vocos_create(const ac_vocos_config* cfg, ac_handle** out);
 
 /* Hand one fp32 tensor to the handle (copied).  `name` uses the HF state-dict keys of
  * EncodecModel with weight-norm either
