@@ -205,6 +205,11 @@ EXPORTS = {
     "ac_resample_stream_push": (_i, [_vp, _sz, _vp, _ll, _i, _i, _ll, _vp, _i, _i, _i, _i, _vp, _ll, _ll, _i, _vp]),
     "ac_resample_stream_reset_slots": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "ac_resample_stream_push_slots": (_i, [_vp, _sz, _i, _vp, _vp, _vp, _vp, _i, _vp, _ll, _i, _vp, _i, _i, _i, _i, _vp, _ll, _ll, _i, _vp]),
+    "ac_knn_packed_bytes": (_sz, [_ll, _i]),
+    "ac_knn_pack": (_i, [_vp, _ll, _i, _vp, _sz, _vp]),
+    "ac_knn_num_splits": (_i, [_ll, _ll, _i, _i]),
+    "ac_knn_workspace_bytes": (_sz, [_ll, _ll, _i, _i, _i]),
+    "ac_knn_match": (_i, [_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

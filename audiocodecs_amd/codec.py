@@ -180,6 +180,23 @@ class Codec(torch.nn.Module, ABC):
         sig = self._polled(self._feats_to_sig(feats, self._ones(feats) if length is None else length))
         return self._out(sig)
 
+    def knn_vc(self, toks, spk_sigs, topk=4):
+        """Single-codebook voice conversion by k-NN feature matching (downstream/test_vc.py:116-128): every quantised feature of `toks`
+        [B, N, 1] is replaced by the mean of its `topk` nearest continuous features (cosine similarity) of the target speaker's signals
+        `spk_sigs` -- a list of [T] or [1, T] signals at `self.sample_rate` -- and the result is decoded: [B, T'].  Built from the
+        public methods and `knn_match` (knn.py) only.  Multi-codebook codecs convert by token splicing (test_vc.py:102-114), which needs
+        no kernel: a `toks` with K != 1 is a ValueError."""
+        from .knn import knn_match
+
+        if toks.dim() != 3 or toks.shape[-1] != 1:
+            raise ValueError(f"knn_vc is the single-codebook conversion: `toks` must be [B, N, 1] (got {tuple(toks.shape)})")
+        if type(self)._feats_to_sig is Codec._feats_to_sig:
+            raise NotImplementedError     # (before any work: this wrapper cannot decode features)
+        if not spk_sigs:
+            raise ValueError("`spk_sigs` is empty: there is nothing to match")
+        matching_set = torch.cat([self.sig_to_feats(s[None] if s.dim() == 1 else s).flatten(end_dim=-2) for s in spk_sigs])
+        return self.feats_to_sig(knn_match(self.toks_to_qfeats(toks), matching_set, topk))
+
     # ---- token-resampling utilities: a step-for-step restatement of /root/reference/audiocodecs/codec.py:121-180 (same RNG call order;
     #      no caller in the reference tree; SURVEY.md section 8 row f2) --------
     def resample(self, toks, p=0.2, temp=1.0, top_k=None, top_p=None):

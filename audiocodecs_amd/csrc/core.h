@@ -5,6 +5,7 @@
 //   mimi_stream.hip streaming Mimi encode and decode: the stream states, one push's launch sequence, its kernels and the ac_mimi_stream_* entry points
 //   encodec_stream.hip streaming EnCodec encode and decode: the stream states (conv histories, the LSTM's h and c), one push's launch sequence,
 //                   the stateful LSTM step kernel and the ac_encodec_stream_* entry points (stream_stage.h / stream_launch.h: what it shares with mimi_stream.hip)
+//   knn.hip         the k-NN feature matcher (knn.h): its kernels and the handle-free ac_knn_* entry points; includes nothing of the above
 //   ac_api.hip      the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once

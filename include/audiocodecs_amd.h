@@ -512,6 +512,39 @@ int ac_resample_stream_push_slots(void* state_dev, size_t state_bytes, int B, co
                                   int L, const float* kern_dev, int n, int o, int taps, int width, float* y_dev, long long y_pitch,
                                   long long y_capacity, int finish, void* stream);
 
+/* Cosine k-nearest-neighbour feature matching: for each of Q query rows [H] the k = min(topk, valid rows) rows of
+ * a matching set [M][H] with the largest cosine similarity, and the mean of those rows -- the single-codebook voice-conversion step of
+ * downstream/test_vc.py:116-128 (`knn(...).mean(dim=-2)`) without its [Q][M] distance matrix, its top-k and its gather.  Both sides are
+ * L2-normalised first and the similarity is ONE dot product of unit vectors in split16 arithmetic (the error of an fp32 FMA chain).
+ * Neighbours are ordered by (similarity descending, index ascending): equal computed similarities go to the lower index.
+ * Handle-free; the caller owns every buffer; all fp32 buffers and the packed image are 16-byte aligned; H is one of 32, 64, 128, 256,
+ * 512 (zero-pad a narrower width: zeros leave the cosine alone); 1 <= topk <= 8; 1 <= M, Q <= 2^24 rows.
+ *   ac_knn_packed_bytes(M, H)      bytes of the packed image of a set (0 for arguments ac_knn_pack refuses).
+ *   ac_knn_pack                    one launch: normalises the rows and writes the image and a validity word per row.  A row whose largest
+ *                                  magnitude is zero or denormal, or that holds an inf or a NaN, is invalid and is never matched.  Pack
+ *                                  once per matching set and match any number of query batches against it.
+ *   ac_knn_num_splits(Q, M, H, n)  the number of slices of the set a match walks side by side: n itself for 1 <= n <= 64, the library's
+ *                                  choice from (Q, M, H) for n = 0 (few queries against a long set: up to 16; 1 from 1024 query waves on and
+ *                                  for sets of at most 240 rows).  Pure host arithmetic; AC_EINVAL for arguments out of range.  Every split count
+ *                                  returns the same indices, similarities and output, bit for bit.
+ *   ac_knn_workspace_bytes         bytes of workspace a match with these arguments needs (0 for arguments it refuses).
+ *   ac_knn_match                   two launches on `stream`.  set_dev is the ORIGINAL fp32 set (the rows that are averaged), packed_dev its
+ *                                  image for the same (M, H).  Any of the results may be NULL:
+ *                                    out_dev [Q][H]     the mean of the k nearest rows: summed nearest first in fp32, times 1 / k
+ *                                    idx_dev [Q][topk]  their indices, nearest first, -1 behind k
+ *                                    sim_dev [Q][topk]  their cosine similarities, NaN behind k
+ *                                  A query row that is invalid in the sense above gets a NaN output row, indices -1 and NaN similarities and
+ *                                  disturbs no other row.
+ * AC_EINVAL for a null or misaligned pointer, a width, topk, row count or split count out of range; AC_ENOMEM for a packed buffer or a
+ * workspace that is too short; all decided on the host before anything is launched.  Nothing allocates or synchronises. */
+size_t ac_knn_packed_bytes(long long M, int H);
+int ac_knn_pack(const float* set_dev, long long M, int H, void* packed_dev, size_t packed_bytes, void* stream);
+int ac_knn_num_splits(long long Q, long long M, int H, int num_splits);
+size_t ac_knn_workspace_bytes(long long Q, long long M, int H, int topk, int num_splits);
+int ac_knn_match(const float* query_dev, long long Q, const float* set_dev, const void* packed_dev, long long M, int H, int topk,
+                 int num_splits, float* out_dev, int64_t* idx_dev, float* sim_dev, void* workspace_dev, size_t workspace_bytes,
+                 void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
