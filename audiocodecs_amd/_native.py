@@ -210,6 +210,13 @@ EXPORTS = {
     "ac_knn_num_splits": (_i, [_ll, _ll, _i, _i]),
     "ac_knn_workspace_bytes": (_sz, [_ll, _ll, _i, _i, _i]),
     "ac_knn_match": (_i, [_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ac_specdist_source_count": (_sz, []),
+    "ac_specdist_source": (_i, [_vp, _sz]),
+    "ac_specdist_tables_bytes": (_sz, []),
+    "ac_specdist_tables": (_i, [_vp, _vp, _sz, _vp]),
+    "ac_specdist_num_frames": (_ll, [_ll]),
+    "ac_specdist_workspace_bytes": (_sz, [_i, _ll, _ll]),
+    "ac_specdist": (_i, [_vp, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

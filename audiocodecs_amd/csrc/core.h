@@ -6,6 +6,8 @@
 //   encodec_stream.hip streaming EnCodec encode and decode: the stream states (conv histories, the LSTM's h and c), one push's launch sequence,
 //                   the stateful LSTM step kernel and the ac_encodec_stream_* entry points (stream_stage.h / stream_launch.h: what it shares with mimi_stream.hip)
 //   knn.hip         the k-NN feature matcher (knn.h): its kernels and the handle-free ac_knn_* entry points; includes nothing of the above
+//   specdist.hip    the fused STFT / mel spectral distances (specdist.h): its kernels, the tables' fp64 source and the handle-free ac_specdist_*
+//                   entry points; includes nothing of the above
 //   ac_api.hip      the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once

@@ -1,0 +1,206 @@
+"""STFT and mel spectral distances: the two resynthesis metrics every evaluation recipe of the reference appends
+(the reference's downstream/metrics/stft_distance.py, mel_distance.py; downstream/test_sr.py:102-142) as one call.
+
+``spectral_distances(hyp_sig, ref_sig, sample_rate)`` resamples both signals to 16 kHz (``audiocodecs_amd.resample``) and returns, per
+clip, the mean over frames of the L2 norm of the dB difference of the two magnitude spectrograms (513 bins) and of the two mel
+spectrograms (80 mels).  It runs in the HIP library (``ac_specdist``): one split16 MFMA GEMM per tile of 16 frames
+with the dB, mel and norm steps in registers -- no spectrogram reaches memory; there is no CPU fallback.  Only the reference's
+defaults are compiled: n_fft = win_length = 1024, hop 320, periodic Hann window, center = True with reflect padding, 80 HTK mel
+filters over 0 .. 8000 Hz without norm, dB = 10 log10(max(x, 1e-10)) without top_db.
+
+``STFTDistance`` and ``MelDistance`` have the reference classes' constructor and ``append``; of speechbrain's ``MetricStats`` only the
+subset below exists (``ids``, ``scores``, ``clear``, ``summarize``).
+
+**Parity with torchaudio's MelSpectrogram / AmplitudeToDB is unpinned**: torchaudio is not on disk, the filterbank and the dB rule are
+restated from its published algorithm.  The STFT part is pinned to ``torch.stft``, which is what the reference calls.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict
+
+import torch
+
+__all__ = ["spectral_distances", "STFTDistance", "MelDistance", "num_frames", "SAMPLE_RATE", "N_FFT", "HOP_LENGTH", "N_MELS", "MAX_HYPS"]
+
+SAMPLE_RATE = 16000
+N_FFT = 1024
+HOP_LENGTH = 320
+N_MELS = 80
+MAX_HYPS = 4          # hypotheses per call
+MAX_LEN = 1 << 24
+
+_TABLES: Dict[int, torch.Tensor] = {}
+
+
+def _check_defaults(n_fft=N_FFT, hop_length=HOP_LENGTH, n_mels=N_MELS) -> None:
+    if (n_fft, hop_length, n_mels) != (N_FFT, HOP_LENGTH, N_MELS):
+        raise ValueError(f"only the reference's defaults are compiled: n_fft={N_FFT}, hop_length={HOP_LENGTH}, n_mels={N_MELS} "
+                         f"(got n_fft={n_fft}, hop_length={hop_length}, n_mels={n_mels})")
+
+
+def num_frames(length_16k: int) -> int:
+    """Frames of a signal of `length_16k` samples at 16 kHz: 1 + L // 320 (center = True)."""
+    if length_16k <= N_FFT // 2:
+        raise ValueError(f"a signal of {length_16k} samples at {SAMPLE_RATE} Hz cannot be reflect-padded by {N_FFT // 2}: it must be longer than that")
+    return 1 + int(length_16k) // HOP_LENGTH
+
+
+def _resampled_len(T: int, sample_rate: int) -> int:
+    import math
+
+    g = math.gcd(int(sample_rate), SAMPLE_RATE)
+    return int(math.ceil((SAMPLE_RATE // g) * T / (int(sample_rate) // g)))
+
+
+def _check_args(hyp_sig, ref_sig, sample_rate):
+    """Everything that can be refused without a GPU.  Returns (P or None, B, T)."""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate < 1:
+        raise ValueError(f"`sample_rate` ({sample_rate!r}) must be a positive int")
+    if not torch.is_tensor(hyp_sig) or not torch.is_tensor(ref_sig):
+        raise ValueError("`hyp_sig` and `ref_sig` must be tensors")
+    if ref_sig.dim() != 2:
+        raise ValueError(f"`ref_sig` must be [B, T] (got {tuple(ref_sig.shape)})")
+    if hyp_sig.dim() not in (2, 3) or tuple(hyp_sig.shape[-2:]) != tuple(ref_sig.shape):
+        raise ValueError(f"`hyp_sig` must be [B, T] or [P, B, T] with the shape of `ref_sig` {tuple(ref_sig.shape)} (got {tuple(hyp_sig.shape)})")
+    P = int(hyp_sig.shape[0]) if hyp_sig.dim() == 3 else None
+    if P is not None and not 1 <= P <= MAX_HYPS:
+        raise ValueError(f"`hyp_sig` holds {P} hypotheses: a call takes 1..{MAX_HYPS}")
+    B, T = (int(n) for n in ref_sig.shape)
+    L16 = _resampled_len(T, sample_rate)
+    if L16 > MAX_LEN:
+        raise ValueError(f"signals of {L16} samples at {SAMPLE_RATE} Hz are longer than the {MAX_LEN} a call takes: split them")
+    num_frames(L16)
+    return P, B, T
+
+
+def _tables(device: torch.device) -> torch.Tensor:
+    """The windowed DFT basis and the filterbank as split16 planes, built once per device from the library's fp64 source."""
+    from . import _native
+
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _TABLES:
+        L = _native.lib()
+        n = L.ac_specdist_source_count()
+        src = torch.empty(n, dtype=torch.float64)
+        _native.check(L.ac_specdist_source(C.c_void_p(src.data_ptr()), n), None, "ac_specdist_source")
+        nbytes = L.ac_specdist_tables_bytes()
+        with torch.cuda.device(idx):
+            src_dev = src.to(torch.device("cuda", idx))
+            tables = torch.empty(nbytes, dtype=torch.uint8, device=src_dev.device)
+            rc = L.ac_specdist_tables(C.c_void_p(src_dev.data_ptr()), C.c_void_p(tables.data_ptr()), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _native.check(rc, None, "ac_specdist_tables")
+            torch.cuda.current_stream().synchronize()      # (once per device: src_dev may go, and other streams may use the tables)
+        _TABLES[idx] = tables
+    return _TABLES[idx]
+
+
+@torch.no_grad()
+def spectral_distances(hyp_sig: torch.Tensor, ref_sig: torch.Tensor, sample_rate: int, return_frames: bool = False):
+    """hyp_sig [B, T] (or [P, B, T]: P hypotheses of the same clips), ref_sig [B, T], both at `sample_rate` -> (stft, mel), each [B]
+    (or [P, B]) fp32 on the signals' device.  With `return_frames` also the per-frame distances the scores are the means of:
+    (stft, mel, stft_frames, mel_frames), the last two [B, F] (or [P, B, F]).  The rows of a [P, B, T] call are bit for bit those of P
+    separate calls; a clip that holds an inf or a NaN gets NaN scores and disturbs no other clip."""
+    from . import _native
+    from .resample import resample
+
+    P, B, T = _check_args(hyp_sig, ref_sig, sample_rate)
+    dev = ref_sig.device
+    lead = () if P is None else (P,)
+    F = num_frames(_resampled_len(T, sample_rate))
+    if B == 0:            # an empty shard: the empty result (the library is not called)
+        out = tuple(torch.empty(lead + (0,), dtype=torch.float32, device=dev) for _ in range(2))
+        return out + tuple(torch.empty(lead + (0, F), dtype=torch.float32, device=dev) for _ in range(2)) if return_frames else out
+    if not (hyp_sig.is_cuda and ref_sig.is_cuda):
+        raise _native.NativeError("audiocodecs_amd.metrics runs on MI355X only: move the signals to a cuda device (there is deliberately no CPU fallback)")
+    if hyp_sig.device != dev:
+        raise ValueError(f"`hyp_sig` is on {hyp_sig.device}, `ref_sig` on {dev}")
+    n = 1 if P is None else P
+    ref = resample(ref_sig.detach().to(torch.float32), sample_rate, SAMPLE_RATE).contiguous()
+    hyp = resample(hyp_sig.detach().to(torch.float32).reshape(n * B, T), sample_rate, SAMPLE_RATE).contiguous()
+    L16 = int(ref.shape[1])
+    L = _native.lib()
+    tables = _tables(dev)
+    stft = torch.empty(n, B, dtype=torch.float32, device=dev)
+    mel = torch.empty(n, B, dtype=torch.float32, device=dev)
+    sfr = torch.empty(n, B, F, dtype=torch.float32, device=dev) if return_frames else None
+    mfr = torch.empty(n, B, F, dtype=torch.float32, device=dev) if return_frames else None
+    nws = L.ac_specdist_workspace_bytes(n, B, L16)
+    if nws == 0:
+        raise ValueError(f"ac_specdist_workspace_bytes refuses P={n}, B={B}, L={L16}")
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.ac_specdist(C.c_void_p(hyp.data_ptr()), C.c_void_p(ref.data_ptr()), n, B, L16, C.c_void_p(tables.data_ptr()), C.c_void_p(stft.data_ptr()),
+                           C.c_void_p(mel.data_ptr()), _native._ptr(sfr), _native._ptr(mfr), C.c_void_p(ws.data_ptr()), nws,
+                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, None, "ac_specdist")
+    shape = lead + (B,)
+    if return_frames:
+        return stft.reshape(shape), mel.reshape(shape), sfr.reshape(shape + (F,)), mfr.reshape(shape + (F,))
+    return stft.reshape(shape), mel.reshape(shape)
+
+
+class _DistanceStats:
+    """The bookkeeping of speechbrain's ``MetricStats`` that the reference's recipes use, and nothing else: ``ids`` and ``scores``
+    (lists, one entry per appended clip), ``clear()`` and ``summarize(field=None)`` with the fields ``average``, ``min_score``,
+    ``min_id``, ``max_score``, ``max_id``.  There is no ``write_stats``, no batch evaluation, no ``n_jobs``."""
+
+    _which = 0           # index into spectral_distances' result
+
+    def clear(self) -> None:
+        self.ids = []
+        self.scores = []
+        self.summary = {}
+
+    @torch.no_grad()
+    def append(self, ids, hyp_sig, ref_sig, lens=None):
+        """`lens` is accepted and ignored, as the reference ignores it."""
+        if not torch.is_tensor(hyp_sig) or not torch.is_tensor(ref_sig) or hyp_sig.shape != ref_sig.shape or hyp_sig.dim() != 2:
+            raise ValueError("`hyp_sig` and `ref_sig` must be [B, T] tensors of the same shape")
+        ids = list(ids)
+        if len(ids) != hyp_sig.shape[0]:
+            raise ValueError(f"{len(ids)} ids for {hyp_sig.shape[0]} clips")
+        scores = spectral_distances(hyp_sig, ref_sig, self.sample_rate)[self._which]
+        self.ids += ids
+        self.scores += scores.cpu().tolist()
+
+    def summarize(self, field=None):
+        if not self.scores:
+            raise ValueError("summarize: nothing was appended")
+        lo = min(range(len(self.scores)), key=self.scores.__getitem__)
+        hi = max(range(len(self.scores)), key=self.scores.__getitem__)
+        self.summary = {
+            "average": float(sum(self.scores) / len(self.scores)),
+            "min_score": float(self.scores[lo]),
+            "min_id": self.ids[lo],
+            "max_score": float(self.scores[hi]),
+            "max_id": self.ids[hi],
+        }
+        return self.summary if field is None else self.summary[field]
+
+
+class STFTDistance(_DistanceStats):
+    """downstream/metrics/stft_distance.py: per clip the mean over frames of the L2 norm over the 513 bins of the dB difference of the
+    two magnitude spectrograms.  Only the subset of ``MetricStats`` that `_DistanceStats` states exists."""
+
+    __doc__ += _DistanceStats.__doc__
+    _which = 0
+
+    def __init__(self, sample_rate, n_fft=N_FFT, hop_length=HOP_LENGTH):
+        _check_defaults(n_fft=n_fft, hop_length=hop_length)
+        self.sample_rate, self.n_fft, self.hop_length = sample_rate, n_fft, hop_length
+        self.clear()
+
+
+class MelDistance(_DistanceStats):
+    """downstream/metrics/mel_distance.py: per clip the mean over frames of the L2 norm over the 80 mels of the dB difference of the
+    two mel spectrograms (power 1).  Only the subset of ``MetricStats`` that `_DistanceStats` states exists."""
+
+    __doc__ += _DistanceStats.__doc__
+    _which = 1
+
+    def __init__(self, sample_rate, n_mels=N_MELS, n_fft=N_FFT, hop_length=HOP_LENGTH):
+        _check_defaults(n_fft=n_fft, hop_length=hop_length, n_mels=n_mels)
+        self.sample_rate, self.n_mels, self.n_fft, self.hop_length = sample_rate, n_mels, n_fft, hop_length
+        self.clear()

@@ -545,6 +545,36 @@ int ac_knn_match(const float* query_dev, long long Q, const float* set_dev, cons
                  int num_splits, float* out_dev, int64_t* idx_dev, float* sim_dev, void* workspace_dev, size_t workspace_bytes,
                  void* stream);
 
+/* Fused STFT and mel spectral distances: the two resynthesis metrics of the reference's evaluation recipes
+ * (downstream/metrics/stft_distance.py:49-69, mel_distance.py:57-61) at their defaults -- signals at 16 kHz, n_fft = win_length = 1024,
+ * hop 320, periodic Hann window, center = True with reflect padding, 513 bins, 80 HTK mel filters over 0 .. 8000 Hz without norm,
+ * dB = 10 log10(max(x, 1e-10)) -- for P hypotheses of B clips against one reference, F = 1 + L / 320 frames a clip:
+ *     stft[p][b] = mean over frames of sqrt(sum over the 513 bins of (dB |X_hyp| - dB |X_ref|)^2),   mel[p][b] likewise over the 80 mels.
+ * One split16 MFMA GEMM per tile of 16 frames with the epilogue in registers: no spectrogram reaches memory, the workspace holds one
+ * fp32 per (hypothesis, clip, frame) and metric.  A clip's results do not depend on P, on B or on the other clips of the call; swapping
+ * hypothesis and reference returns the same bits; equal signals give exactly 0; a clip that holds an inf or a NaN gets NaN scores and
+ * disturbs no other clip.  Handle-free; the caller owns every buffer; the source, the tables and the workspace are 16-byte aligned, signals
+ * and results 4-byte (a row of a larger batch serves as it stands); 1 <= P <= 4, 1 <= B,
+ * 512 < L <= 2^24 (and P B ceil(F / 16) < 2^31).
+ *   ac_specdist_source_count()     doubles of the tables' fp64 source: cos(2 pi j / 1024) [1024], then the filterbank [513][80].
+ *   ac_specdist_source             fills that source in HOST memory (pure host arithmetic in fp64, angles reduced as integers; no GPU).
+ *   ac_specdist_tables_bytes()     bytes of the device tables (the windowed DFT basis and the filterbank as split16 fp16 planes).
+ *   ac_specdist_tables             one launch: builds the tables from the caller's DEVICE copy of the source.  Build once per device.
+ *   ac_specdist_num_frames(L)      F (0 for an L that ac_specdist refuses).
+ *   ac_specdist_workspace_bytes    bytes of workspace a call with these arguments needs (0 for arguments it refuses).
+ *   ac_specdist                    two launches on `stream`.  hyp_dev [P][B][L], ref_dev [B][L], stft_out / mel_out [P][B];
+ *                                  stft_frames_out / mel_frames_out [P][B][F] (the per-frame distances) may be NULL.
+ * AC_EINVAL for a null or misaligned pointer, a count out of range or L <= 512; AC_ENOMEM for a table buffer or a workspace that is too
+ * short; all decided on the host before anything is launched.  Nothing allocates or synchronises. */
+size_t ac_specdist_source_count(void);
+int ac_specdist_source(double* src_host, size_t count);
+size_t ac_specdist_tables_bytes(void);
+int ac_specdist_tables(const double* src_dev, void* tables_dev, size_t tables_bytes, void* stream);
+long long ac_specdist_num_frames(long long L);
+size_t ac_specdist_workspace_bytes(int P, long long B, long long L);
+int ac_specdist(const float* hyp_dev, const float* ref_dev, int P, long long B, long long L, const void* tables_dev, float* stft_out,
+                float* mel_out, float* stft_frames_out, float* mel_frames_out, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
