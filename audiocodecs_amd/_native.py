@@ -217,6 +217,13 @@ EXPORTS = {
     "ac_specdist_num_frames": (_ll, [_ll]),
     "ac_specdist_workspace_bytes": (_sz, [_i, _ll, _ll]),
     "ac_specdist": (_i, [_vp, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ac_stoi_source_count": (_sz, []),
+    "ac_stoi_source": (_i, [_vp, _sz]),
+    "ac_stoi_tables_bytes": (_sz, []),
+    "ac_stoi_tables": (_i, [_vp, _vp, _sz, _vp]),
+    "ac_stoi_num_frames": (_ll, [_ll]),
+    "ac_stoi_workspace_bytes": (_sz, [_i, _ll, _ll]),
+    "ac_stoi": (_i, [_vp, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

@@ -8,7 +8,9 @@
 //   knn.hip         the k-NN feature matcher (knn.h): its kernels and the handle-free ac_knn_* entry points; includes nothing of the above
 //   specdist.hip    the fused STFT / mel spectral distances (specdist.h): its kernels, the tables' fp64 source and the handle-free ac_specdist_*
 //                   entry points; includes nothing of the above
-//   ac_api.hip      the extern "C" entry points of include/audiocodecs_amd.h
+//   stoi.hip        the fused STOI (stoi.h): its kernels, the tables' fp64 source and the handle-free ac_stoi_* entry points; includes nothing of
+//                   the above and reaches the FIR through the public ac_resample
+//   ac_api.hip     the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -13,6 +13,16 @@ subset below exists (``ids``, ``scores``, ``clear``, ``summarize``).
 
 **Parity with torchaudio's MelSpectrogram / AmplitudeToDB is unpinned**: torchaudio is not on disk, the filterbank and the dB rule are
 restated from its published algorithm.  The STFT part is pinned to ``torch.stft``, which is what the reference calls.
+
+``stoi(hyp_sig, ref_sig, sample_rate)`` is the third signal-processing metric of those recipes (downstream/metrics/stoi.py: torchmetrics
+calling pystoi clip by clip on the host) as one call on the device (``ac_stoi``): both signals to 16 kHz, pystoi's
+second resampling to 10 kHz, the removal of the frames more than 40 dB below the reference's loudest, overlap-add, a 512-point STFT as a
+split16 MFMA GEMM, 15 third-octave band envelopes and the clipped, normalised correlation over segments of 30 frames.  The number of kept
+frames is never read back by the host.  ``ref_sig`` is pystoi's clean signal x: the score is not symmetric.  Only ``extended=False`` is
+compiled.  ``STOI`` has the reference class's constructor and ``append``.
+
+**Parity with pystoi is unpinned**: neither pystoi nor torchmetrics is on disk; the FIR, the window, the band edges and every step are
+restated from pystoi's published algorithm (tests/stoi_ref.py is that statement in fp64; the FIR is pinned to scipy.signal.resample_poly).
 """
 
 from __future__ import annotations
@@ -22,7 +32,7 @@ from typing import Dict
 
 import torch
 
-__all__ = ["spectral_distances", "STFTDistance", "MelDistance", "num_frames", "SAMPLE_RATE", "N_FFT", "HOP_LENGTH", "N_MELS", "MAX_HYPS"]
+__all__ = ["spectral_distances", "STFTDistance", "MelDistance", "stoi", "STOI", "num_frames", "stoi_num_frames", "SAMPLE_RATE", "N_FFT", "HOP_LENGTH", "N_MELS", "MAX_HYPS"]
 
 SAMPLE_RATE = 16000
 N_FFT = 1024
@@ -161,9 +171,12 @@ class _DistanceStats:
         ids = list(ids)
         if len(ids) != hyp_sig.shape[0]:
             raise ValueError(f"{len(ids)} ids for {hyp_sig.shape[0]} clips")
-        scores = spectral_distances(hyp_sig, ref_sig, self.sample_rate)[self._which]
+        scores = self._scores(hyp_sig, ref_sig)
         self.ids += ids
         self.scores += scores.cpu().tolist()
+
+    def _scores(self, hyp_sig, ref_sig):
+        return spectral_distances(hyp_sig, ref_sig, self.sample_rate)[self._which]
 
     def summarize(self, field=None):
         if not self.scores:
@@ -204,3 +217,125 @@ class MelDistance(_DistanceStats):
         _check_defaults(n_fft=n_fft, hop_length=hop_length, n_mels=n_mels)
         self.sample_rate, self.n_mels, self.n_fft, self.hop_length = sample_rate, n_mels, n_fft, hop_length
         self.clear()
+
+
+# ---- STOI ------------------------------------------------------------------------------------------------------------------------------
+STOI_MIN_LEN_10K = 256          # one frame at 10 kHz
+STOI_SEGMENT = 30               # frames per segment
+
+_STOI_TABLES: Dict[int, torch.Tensor] = {}
+
+
+def stoi_num_frames(length_16k: int) -> int:
+    """Frames of 256 at hop 128 of a signal of `length_16k` samples at 16 kHz once it stands at 10 kHz (before the silent ones go):
+    (ceil(5 L / 8) - 256) // 128 + 1."""
+    L10 = -(-5 * int(length_16k) // 8)
+    if L10 < STOI_MIN_LEN_10K:
+        raise ValueError(f"a signal of {length_16k} samples at {SAMPLE_RATE} Hz is {L10} samples at 10 kHz: STOI needs one frame of {STOI_MIN_LEN_10K}")
+    return (L10 - STOI_MIN_LEN_10K) // 128 + 1
+
+
+def _check_stoi_args(hyp_sig, ref_sig, sample_rate, extended):
+    """Everything that can be refused without a GPU.  Returns (P or None, B, T, F0)."""
+    if extended is not False:
+        raise ValueError(f"only the reference's default is compiled: extended=False (got extended={extended!r})")
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate < 1:
+        raise ValueError(f"`sample_rate` ({sample_rate!r}) must be a positive int")
+    if not torch.is_tensor(hyp_sig) or not torch.is_tensor(ref_sig):
+        raise ValueError("`hyp_sig` and `ref_sig` must be tensors")
+    if ref_sig.dim() != 2:
+        raise ValueError(f"`ref_sig` must be [B, T] (got {tuple(ref_sig.shape)})")
+    if hyp_sig.dim() not in (2, 3) or tuple(hyp_sig.shape[-2:]) != tuple(ref_sig.shape):
+        raise ValueError(f"`hyp_sig` must be [B, T] or [P, B, T] with the shape of `ref_sig` {tuple(ref_sig.shape)} (got {tuple(hyp_sig.shape)})")
+    P = int(hyp_sig.shape[0]) if hyp_sig.dim() == 3 else None
+    if P is not None and not 1 <= P <= MAX_HYPS:
+        raise ValueError(f"`hyp_sig` holds {P} hypotheses: a call takes 1..{MAX_HYPS}")
+    B, T = (int(n) for n in ref_sig.shape)
+    L16 = _resampled_len(T, sample_rate)
+    if L16 > MAX_LEN:
+        raise ValueError(f"signals of {L16} samples at {SAMPLE_RATE} Hz are longer than the {MAX_LEN} a call takes: split them")
+    return P, B, T, stoi_num_frames(L16)
+
+
+def _stoi_tables(device: torch.device) -> torch.Tensor:
+    """The window, the 16 -> 10 kHz FIR bank and the windowed DFT basis (split16 planes), built once per device from the library's fp64 source."""
+    from . import _native
+
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _STOI_TABLES:
+        L = _native.lib()
+        n = L.ac_stoi_source_count()
+        src = torch.empty(n, dtype=torch.float64)
+        _native.check(L.ac_stoi_source(C.c_void_p(src.data_ptr()), n), None, "ac_stoi_source")
+        nbytes = L.ac_stoi_tables_bytes()
+        with torch.cuda.device(idx):
+            src_dev = src.to(torch.device("cuda", idx))
+            tables = torch.empty(nbytes, dtype=torch.uint8, device=src_dev.device)
+            rc = L.ac_stoi_tables(C.c_void_p(src_dev.data_ptr()), C.c_void_p(tables.data_ptr()), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _native.check(rc, None, "ac_stoi_tables")
+            torch.cuda.current_stream().synchronize()      # (once per device: src_dev may go, and other streams may use the tables)
+        _STOI_TABLES[idx] = tables
+    return _STOI_TABLES[idx]
+
+
+@torch.no_grad()
+def stoi(hyp_sig: torch.Tensor, ref_sig: torch.Tensor, sample_rate: int, extended: bool = False, return_details: bool = False):
+    """hyp_sig [B, T] (or [P, B, T]: P hypotheses of the same clips), ref_sig [B, T] (the clean signal), both at `sample_rate` -> the STOI
+    score [B] (or [P, B]) fp32 on the signals' device.  With `return_details` (score, kept, num_segments, segments): kept [B, F0] bool,
+    the frames the silent-frame rule keeps; num_segments [B] int32; segments [B, max(F0 - 30, 0)] (or [P, B, ...]) fp32, per segment the
+    sum of the 15 band correlations / 15, NaN past num_segments.  Fewer than 30 frames left give 1e-5, as pystoi does.  The rows of a
+    [P, B, T] call are bit for bit those of P separate calls; a clip that holds an inf or a NaN gets a NaN score and disturbs no other."""
+    from . import _native
+    from .resample import resample
+
+    P, B, T, F0 = _check_stoi_args(hyp_sig, ref_sig, sample_rate, extended)
+    dev = ref_sig.device
+    lead = () if P is None else (P,)
+    NS0 = max(F0 - STOI_SEGMENT, 0)
+    if B == 0:            # an empty shard: the empty result (the library is not called)
+        score = torch.empty(lead + (0,), dtype=torch.float32, device=dev)
+        if not return_details:
+            return score
+        return (score, torch.empty(0, F0, dtype=torch.bool, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(lead + (0, NS0), dtype=torch.float32, device=dev))
+    if not (hyp_sig.is_cuda and ref_sig.is_cuda):
+        raise _native.NativeError("audiocodecs_amd.metrics runs on MI355X only: move the signals to a cuda device (there is deliberately no CPU fallback)")
+    if hyp_sig.device != dev:
+        raise ValueError(f"`hyp_sig` is on {hyp_sig.device}, `ref_sig` on {dev}")
+    n = 1 if P is None else P
+    ref = resample(ref_sig.detach().to(torch.float32), sample_rate, SAMPLE_RATE).contiguous()
+    hyp = resample(hyp_sig.detach().to(torch.float32).reshape(n * B, T), sample_rate, SAMPLE_RATE).contiguous()
+    L16 = int(ref.shape[1])
+    L = _native.lib()
+    tables = _stoi_tables(dev)
+    score = torch.empty(n, B, dtype=torch.float32, device=dev)
+    kept = torch.empty(B, F0, dtype=torch.bool, device=dev) if return_details else None
+    nseg = torch.empty(B, dtype=torch.int32, device=dev) if return_details else None
+    segs = torch.empty(n, B, NS0, dtype=torch.float32, device=dev) if return_details else None
+    nws = L.ac_stoi_workspace_bytes(n, B, L16)
+    if nws == 0:
+        raise ValueError(f"ac_stoi_workspace_bytes refuses P={n}, B={B}, L16={L16}")
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.ac_stoi(C.c_void_p(hyp.data_ptr()), C.c_void_p(ref.data_ptr()), n, B, L16, C.c_void_p(tables.data_ptr()), C.c_void_p(score.data_ptr()),
+                       _native._ptr(kept), _native._ptr(nseg), _native._ptr(segs), C.c_void_p(ws.data_ptr()), nws,
+                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, None, "ac_stoi")
+    shape = lead + (B,)
+    if return_details:
+        return score.reshape(shape), kept, nseg, segs.reshape(shape + (NS0,))
+    return score.reshape(shape)
+
+
+class STOI(_DistanceStats):
+    """downstream/metrics/stoi.py: per clip the short-time objective intelligibility of `hyp_sig` against the clean `ref_sig` (pystoi's
+    defaults, extended = False).  Only the subset of ``MetricStats`` that `_DistanceStats` states exists."""
+
+    __doc__ += _DistanceStats.__doc__
+
+    def __init__(self, sample_rate):
+        self.sample_rate = sample_rate
+        self.clear()
+
+    def _scores(self, hyp_sig, ref_sig):
+        return stoi(hyp_sig, ref_sig, self.sample_rate)

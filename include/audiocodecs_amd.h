@@ -575,6 +575,34 @@ size_t ac_specdist_workspace_bytes(int P, long long B, long long L);
 int ac_specdist(const float* hyp_dev, const float* ref_dev, int P, long long B, long long L, const void* tables_dev, float* stft_out,
                 float* mel_out, float* stft_frames_out, float* mel_frames_out, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* STOI of P hypotheses of B clips against one reference: downstream/metrics/stoi.py behind its resampling to
+ * 16 kHz -- pystoi's algorithm at its defaults (extended = False), restated: 16 -> 10 kHz by a Kaiser-windowed polyphase FIR (581 taps, up 5,
+ * down 8), removal of the frames of 256 at hop 128 that lie more than 40 dB below the loudest frame of the REFERENCE, overlap-add of the
+ * kept frames of both signals, 512-point STFT, 15 third-octave band envelopes, the clipped and normalised correlation over sliding
+ * segments of 30 frames.  All signals are fp32 at 16 kHz with L16 samples, ceil(5 L16 / 8) >= 256 and L16 <= 2^24;
+ * F0 = (ceil(5 L16 / 8) - 256) / 128 + 1 frames exist before the removal; 1 <= P <= 4.  The score of a pair with fewer than 30 STFT frames
+ * left is 1e-5; a clip with an inf or a NaN in either signal gets NaN.  A clip's values depend on nothing else in the call.
+ *   ac_stoi_source_count()      doubles of the tables' fp64 source: hanning(258)[1:-1] [256], cos(2 pi j / 512) [512], the FIR h [581].
+ *   ac_stoi_source              fills that source in HOST memory (pure host arithmetic in fp64; no GPU).
+ *   ac_stoi_tables_bytes()      bytes of the device tables (window and FIR bank in fp32, the windowed DFT basis as split16 fp16 planes).
+ *   ac_stoi_tables              one launch: builds the tables from the caller's DEVICE copy of the source.  Build once per device.
+ *   ac_stoi_num_frames(L16)     F0 (0 for an L16 that ac_stoi refuses).
+ *   ac_stoi_workspace_bytes     bytes of workspace a call with these arguments needs (0 for arguments it refuses).
+ *   ac_stoi                     six launches on `stream`, none sized by anything the device computes.  hyp_dev [P][B][L16],
+ *                               ref_dev [B][L16], score_out [P][B].  Optional (may be NULL): kept_out [B][F0] bytes 0 / 1, the frames
+ *                               kept; num_segments_out [B], S = max(K - 30, 0) for K kept frames; segments_out [P][B][max(F0 - 30, 0)],
+ *                               per segment the sum of the 15 band correlations / 15, NaN past S.
+ * AC_EINVAL for a null or misaligned pointer, a count out of range or a length out of range; AC_ENOMEM for a table buffer or a
+ * workspace that is too short; all decided on the host before anything is launched.  Nothing allocates or synchronises. */
+size_t ac_stoi_source_count(void);
+int ac_stoi_source(double* src_host, size_t count);
+size_t ac_stoi_tables_bytes(void);
+int ac_stoi_tables(const double* src_dev, void* tables_dev, size_t tables_bytes, void* stream);
+long long ac_stoi_num_frames(long long L16);
+size_t ac_stoi_workspace_bytes(int P, long long B, long long L16);
+int ac_stoi(const float* hyp_dev, const float* ref_dev, int P, long long B, long long L16, const void* tables_dev, float* score_out,
+            uint8_t* kept_out, int32_t* num_segments_out, float* segments_out, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */

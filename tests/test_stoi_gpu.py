@@ -1,0 +1,301 @@
+"""GPU tests of the fused STOI (audiocodecs_amd.stoi, csrc/stoi.h) against the fp64 statement of tests/stoi_ref.py.
+
+The silent-frame mask and the number of segments must equal the statement's exactly.  That is a condition on the CASES, not a measurement:
+before the device is called every case asserts on the CPU that no frame energy of its reference lies within 0.01 dB of the 40 dB rule
+(fp32 rounding of a frame energy is about 1e-5 dB), so the mask is not a draw.  With the seeds 17 L + 5 b the worst margin over the
+sweep is 0.08 dB.
+
+The tolerance of the scores is MEASURED, not fixed: per signal kind, the largest absolute error of the same statement run in numpy float32
+against fp64 over that kind's sweep cases, per clip and per segment separately; the kernel gets 4 x that (split16 drops the lo lo term,
+2^-22 of a product where fp32 rounds at 2^-24; nothing else in the chain is looser than fp32).  Independence, [P, B, T] against P calls
+and graph replay ask for identical bits.
+
+The kernel's frame tile is 16 STFT frames and K kept frames give K - 1 of them: K - 1 = 29 (the 1e-5 path), 30, 31 (partial second
+tile), 32 (two full tiles), 33 (a tile of one frame), 48, 49 (the next seam), 76; `gaps`, `late` and `fade` put the boundaries of the
+kept runs inside a tile.  Figures of the run that DESIGN.md section 8k quotes are in the parity record (`stoi/...`)."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import parity_record
+import stoi_ref as R
+
+pytestmark = pytest.mark.gpu
+
+LENGTHS = {
+    "steady": [6552, 6553, 6759, 6964, 7168, 10240, 10445, 16000],
+    "gaps": [8000, 9000, 12000, 16000, 24000],
+    "late": [8000, 9000, 12000, 16000],
+    "fade": [12000, 16000, 20000, 24000],
+}
+STEADY_K = [30, 31, 32, 33, 34, 49, 50, 77]
+SWEEP = [(kind, L, B, P) for kind in R.KINDS for L in LENGTHS[kind] for B in (1, 3) for P in (1, 3)]
+FACTOR = 4.0
+MIN_MARGIN_DB = 0.01
+
+
+@functools.lru_cache(maxsize=None)
+def clip(kind, L, b):
+    """The reference of clip b (1-based) of a (kind, L): fp32 [L], read-only."""
+    x = R.make_ref(kind, L, 1, first=b)[0]
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def pair(kind, L, b, p):
+    """(hyp fp32 [L], fp64 details, fp32 details) of hypothesis p of clip b: computed once, shared by every test that needs it."""
+    ref = clip(kind, L, b)
+    hyp = R.make_hyp(ref[None], L, p, first=b)[0]
+    hyp.setflags(write=False)
+    return hyp, R.details(hyp, ref), R.details(hyp, ref, np.float32)
+
+
+def case_data(kind, L, B, P):
+    """(hyp [P, B, L], ref [B, L]) of a sweep case: clips 1 .. B, hypotheses 0 .. P - 1."""
+    return np.stack([np.stack([pair(kind, L, b, p)[0] for b in range(1, B + 1)]) for p in range(P)]), np.stack([clip(kind, L, b) for b in range(1, B + 1)])
+
+
+def seg_err(got, want):
+    return float(np.abs(np.asarray(got, dtype=np.float64) - want).max()) if len(want) else 0.0
+
+
+class Sweep:
+    """Computed once: the fp32 statement's error against fp64 per kind (per clip, per segment) over that kind's sweep cases."""
+
+    def __init__(self):
+        self.fp32_err = {k: [0.0, 0.0] for k in R.KINDS}
+        for kind in R.KINDS:
+            for L in LENGTHS[kind]:
+                for b in (1, 2, 3):
+                    for p in range(3):
+                        _, d64, d32 = pair(kind, L, b, p)
+                        assert np.array_equal(d64["kept"], d32["kept"])
+                        e = self.fp32_err[kind]
+                        self.fp32_err[kind] = [max(e[0], abs(d32["score"] - d64["score"])), max(e[1], seg_err(d32["segments"], d64["segments"]))]
+        self.kernel_err = {k: [0.0, 0.0] for k in R.KINDS}
+
+    def tol(self, kind):
+        return FACTOR * self.fp32_err[kind][0], FACTOR * self.fp32_err[kind][1]
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    return Sweep()
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def run(hyp, ref, sample_rate=16000):
+    from audiocodecs_amd import stoi
+
+    out = stoi(dev(hyp), dev(ref), sample_rate, return_details=True)
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in out)
+
+
+def bits(a):
+    return a.view(np.uint8) if a.dtype == np.bool_ else a.view(np.uint32)
+
+
+def same_bits(a, b):
+    return all(x.shape == y.shape and np.array_equal(bits(x), bits(y)) for x, y in zip(a, b))
+
+
+def test_sweep_covers_every_tile_count_and_kind():
+    assert [R.num_frames(L) for L in LENGTHS["steady"]] == STEADY_K
+    assert [pair("steady", L, 1, 0)[1]["K"] for L in LENGTHS["steady"]] == STEADY_K      # nothing is silent: K = F0
+    assert {c[0] for c in SWEEP} == set(R.KINDS) and {c[2] for c in SWEEP} == {1, 3} and {c[3] for c in SWEEP} == {1, 3}
+    for kind in ("gaps", "late", "fade"):
+        for L in LENGTHS[kind]:
+            d = pair(kind, L, 1, 0)[1]
+            assert d["K"] < R.num_frames(L), (kind, L)
+    assert [pair("fade", L, 1, 0)[1]["K"] for L in LENGTHS["fade"]] == [30, 40, 49, 59]
+    assert all(int(np.flatnonzero(pair("late", L, b, 0)[1]["kept"])[0]) in (6, 7) for L in LENGTHS["late"] for b in (1, 2, 3))
+
+
+@pytest.mark.parametrize("kind,L,B,P", SWEEP)
+def test_shape_sweep(sweep, kind, L, B, P):
+    hyp, ref = case_data(kind, L, B, P)
+    want = [[pair(kind, L, b, p)[1] for b in range(1, B + 1)] for p in range(P)]
+    margin = min(d["margin"] for d in want[0])
+    assert margin >= MIN_MARGIN_DB, f"a frame energy lies {margin:.4f} dB from the silent-frame rule: the mask of this case would be a draw"
+    score, kept, nseg, segs = run(hyp if P > 1 else hyp[0], ref)
+    F0 = R.num_frames(L)
+    lead = (P,) if P > 1 else ()
+    assert score.shape == lead + (B,) and kept.shape == (B, F0) and nseg.shape == (B,) and segs.shape == lead + (B, max(F0 - 30, 0))
+    assert score.dtype == np.float32 and kept.dtype == np.bool_ and nseg.dtype == np.int32 and segs.dtype == np.float32
+    score, segs = score.reshape(P, B), segs.reshape(P, B, -1)
+    clip_e = seg_e = 0.0
+    for b in range(B):
+        d = want[0][b]
+        assert np.array_equal(kept[b], d["kept"]), f"clip {b}: the silent-frame mask differs at frames {np.flatnonzero(kept[b] != d['kept'])}"
+        assert nseg[b] == d["S"]
+        for p in range(P):
+            d = want[p][b]
+            assert np.isnan(segs[p, b, d["S"]:]).all() and not np.isnan(segs[p, b, :d["S"]]).any()
+            clip_e = max(clip_e, abs(float(score[p, b]) - d["score"]))
+            seg_e = max(seg_e, seg_err(segs[p, b, :d["S"]], d["segments"]))
+    tol = sweep.tol(kind)
+    sweep.kernel_err[kind] = [max(sweep.kernel_err[kind][0], clip_e), max(sweep.kernel_err[kind][1], seg_e)]
+    print(f"stoi sweep {kind} L={L} B={B} P={P}: kernel clip {clip_e:.3e} segment {seg_e:.3e}; fp32 statement (kind's worst) clip {sweep.fp32_err[kind][0]:.3e} "
+          f"segment {sweep.fp32_err[kind][1]:.3e}; tolerance clip {tol[0]:.3e} segment {tol[1]:.3e}; margin {margin:.3f} dB")
+    parity_record.record("stoi", f"sweep/{kind}_L{L}_B{B}_P{P}", kernel_clip_err=clip_e, kernel_segment_err=seg_e, fp32_clip_err=sweep.fp32_err[kind][0],
+                         fp32_segment_err=sweep.fp32_err[kind][1], clip_tol=tol[0], segment_tol=tol[1], margin_db=margin)
+    assert clip_e <= tol[0] and seg_e <= tol[1]
+
+
+def test_a_clip_does_not_depend_on_its_company():
+    from audiocodecs_amd import stoi
+
+    hyp, ref = case_data("gaps", 12000, 3, 3)
+    whole = run(hyp, ref)                                   # score [3, 3], kept [3, F0], nseg [3], segments [3, 3, F0 - 30]
+    assert same_bits(whole, run(hyp, ref)), "two runs"
+    for p in range(3):
+        one = run(hyp[p], ref)                              # P separate calls
+        assert same_bits((whole[0][p], whole[1], whole[2], whole[3][p]), one), f"hypothesis {p} alone"
+    alone = run(hyp[1, 2:3], ref[2:3])                      # B = 1
+    assert same_bits((whole[0][1, 2:3], whole[1][2:3], whole[2][2:3], whole[3][1, 2:3]), alone), "clip 2 alone"
+    d_h, d_r = dev(hyp), dev(ref)
+    view = stoi(d_h[1, 2:3], d_r[2:3], 16000, return_details=True)      # a row of the larger batch as it stands
+    assert same_bits(alone, [t.cpu().numpy() for t in view])
+
+
+def test_replays_from_a_captured_graph():
+    from audiocodecs_amd import stoi
+
+    hyp, ref = case_data("late", 16000, 3, 2)
+    sh, sr = dev(hyp[0]), dev(ref)
+    eager = stoi(sh, sr, 16000, return_details=True)        # (also builds the tables: a capture cannot)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(g, stream=side):
+            so = stoi(sh, sr, 16000, return_details=True)
+    torch.cuda.current_stream().wait_stream(side)
+    for data, want in ((hyp[0], eager), (hyp[1], None), (hyp[0], eager)):
+        sh.copy_(dev(data))
+        g.replay()
+        torch.cuda.synchronize()
+        if want is None:
+            want = stoi(dev(data), sr, 16000, return_details=True)
+        assert same_bits([t.cpu().numpy() for t in so], [t.cpu().numpy() for t in want])
+
+
+def test_identical_signals_score_one(sweep):
+    ref = case_data("steady", 10445, 2, 1)[1]
+    score = run(ref, ref)[0]
+    err = float(np.abs(score.astype(np.float64) - 1.0).max())
+    parity_record.record("stoi", "identity", kernel_clip_err=err, clip_tol=sweep.tol("steady")[0])
+    assert err <= sweep.tol("steady")[0]
+
+
+def test_all_zero_reference_is_finite():
+    hyp = case_data("steady", 8000, 2, 1)[1]
+    ref = hyp.copy()
+    ref[1] = 0.0
+    score, kept, nseg, segs = run(hyp, ref)
+    assert np.isfinite(score).all() and kept[1].all() and nseg[1] == R.num_frames(8000) - 30
+    assert abs(float(score[1])) <= 1e-6 and abs(float(score[0]) - 1.0) <= 1e-5
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+def test_a_bad_sample_spoils_its_clip_only(bad):
+    L = 9000
+    hyp, ref = case_data("late", L, 3, 1)
+    hyp = hyp[0]
+    clean = run(hyp, ref)
+    for where in (0, L // 2, L - 1):                        # (the first sample of `late` lies in a frame the rule drops: the clip is spoilt all the same)
+        for side in ("hyp", "ref"):
+            h, r = hyp.copy(), ref.copy()
+            (h if side == "hyp" else r)[1, where] = bad
+            got = run(h, r)
+            assert np.isnan(got[0][1]), (where, side)
+            assert same_bits([g[[0, 2]] for g in got], [g[[0, 2]] for g in clean]), (where, side)
+
+
+def test_resampled_path(sweep):
+    from audiocodecs_amd.resample import resample
+
+    L = 24000
+    ref = R.make_ref("steady", L, 2)
+    hyp = R.make_hyp(ref, L, 1)
+    got = run(hyp, ref, 24000)
+    h16, r16 = (resample(dev(x), 24000, 16000).cpu().numpy() for x in (hyp, ref))
+    assert h16.shape == (2, 16000) and got[1].shape == (2, 77)
+    assert same_bits(got, run(h16, r16))
+    clip_e = seg_e = 0.0
+    for b in range(2):
+        d = R.details(h16[b], r16[b])
+        assert d["margin"] >= MIN_MARGIN_DB and np.array_equal(got[1][b], d["kept"]) and got[2][b] == d["S"]
+        clip_e, seg_e = max(clip_e, abs(float(got[0][b]) - d["score"])), max(seg_e, seg_err(got[3][b, :d["S"]], d["segments"]))
+    tol = sweep.tol("steady")
+    parity_record.record("stoi", "resampled_24k", kernel_clip_err=clip_e, kernel_segment_err=seg_e, clip_tol=tol[0], segment_tol=tol[1])
+    assert clip_e <= tol[0] and seg_e <= tol[1]
+
+
+def test_abi_refusals_launch_nothing():
+    from audiocodecs_amd import _native, metrics
+
+    lib = _native.lib()
+    P, B, L = 1, 2, 8000
+    hyp, ref = case_data("gaps", L, B, 1)
+    hyp, ref = dev(hyp[0]), dev(ref)
+    F0 = R.num_frames(L)
+    tables = metrics._stoi_tables(hyp.device)
+    nws = lib.ac_stoi_workspace_bytes(P, B, L)
+    ws = torch.zeros(nws + 16, dtype=torch.uint8, device="cuda")
+    score = torch.full((B,), 7.0, device="cuda")
+    kept = torch.full((B, F0), 7, dtype=torch.uint8, device="cuda")
+    nseg = torch.full((B,), 7, dtype=torch.int32, device="cuda")
+    segs = torch.full((B, F0 - 30), 7.0, device="cuda")
+    p = lambda x, o=0: C.c_void_p(x.data_ptr() + o)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    args = lambda **kw: [kw.get("hyp", p(hyp)), kw.get("ref", p(ref)), kw.get("P", P), kw.get("B", B), kw.get("L", L), kw.get("tab", p(tables)), kw.get("out", p(score)), p(kept),
+                         kw.get("nseg", p(nseg)), kw.get("segs", p(segs)), kw.get("ws", p(ws)), kw.get("nws", nws), st]
+    for kw in (dict(hyp=None), dict(ref=None), dict(tab=None), dict(out=None), dict(ws=None), dict(hyp=p(hyp, 2)), dict(ref=p(ref, 1)), dict(tab=p(tables, 4)), dict(ws=p(ws, 8)),
+               dict(out=p(score, 2)), dict(nseg=p(nseg, 2)), dict(segs=p(segs, 1)), dict(L=408), dict(L=0), dict(L=(1 << 24) + 1), dict(P=5), dict(P=0), dict(B=0)):
+        assert lib.ac_stoi(*args(**kw)) == -1, kw
+    assert lib.ac_stoi(*args(nws=nws - 1)) == -3
+    assert lib.ac_stoi_tables(p(tables), p(tables), lib.ac_stoi_tables_bytes() - 1, st) == -3
+    torch.cuda.synchronize()
+    assert (score == 7.0).all() and (kept == 7).all() and (nseg == 7).all() and (segs == 7.0).all() and (ws == 0).all(), "a refused call launched"
+    assert lib.ac_stoi(*args()) == 0
+    torch.cuda.synchronize()
+    want = run(hyp.cpu().numpy(), ref.cpu().numpy())
+    assert same_bits((score.cpu().numpy(), kept.cpu().numpy().astype(np.bool_), nseg.cpu().numpy(), segs.cpu().numpy()), want)
+
+
+def test_metric_class_on_the_device():
+    from audiocodecs_amd import STOI
+
+    L = 10800
+    ref = R.make_ref("steady", L, 2)
+    hyp = R.make_hyp(ref, L, 1)
+    want = run(hyp, ref, 24000)[0]
+    met = STOI(24000)
+    met.append(["x", "y"], dev(hyp), dev(ref), lens=torch.ones(2))
+    assert met.ids == ["x", "y"] and met.scores == want.tolist()
+    assert met.summarize("average") == pytest.approx(float(np.mean(want.astype(np.float64))))
+
+
+def test_resynthesis_stoi_is_the_chain_of_public_calls(checkpoints):
+    from audiocodecs_amd import Encodec, stoi
+
+    cfg, sd = checkpoints("tiny", 0)
+    codec = Encodec(24000, num_codebooks=8, state_dict=sd, config=cfg).eval()
+    sig = dev(R.make_ref("steady", 12001, 2))
+    score = codec.resynthesis_stoi(sig)
+    assert score.shape == (2,) and score.dtype == torch.float32 and bool(torch.isfinite(score).all())
+    rec = codec.toks_to_sig(codec.sig_to_toks(sig))
+    T = sig.shape[-1]
+    rec = torch.nn.functional.pad(rec, [0, T - rec.shape[-1]], mode="replicate") if rec.shape[-1] < T else rec.narrow(-1, 0, T)
+    assert torch.equal(score, stoi(rec, sig, 24000))
+    parity_record.record("stoi", "resynthesis/encodec_tiny", stoi=float(score.mean()))
