@@ -3,6 +3,7 @@
 from .codec import Codec
 from .config import DAC_16KHZ, DAC_24KHZ, DAC_44KHZ, DAC_TINY, ENCODEC_24KHZ, MIMI_24KHZ, MIMI_TINY, TINY, VOCOS_ENCODEC_24KHZ, VOCOS_TINY, WAVTOK_40, WAVTOK_75, WAVTOK_TINY, DacConfig, EncodecConfig, MimiConfig, VocosConfig, WavTokenizerConfig
 from .dac import DAC
+from .dnsmos import DNSMOS, DnsmosWeights, dnsmos, dnsmos_net, dnsmos_segments
 from .encodec import Encodec, EncodecDecodeSessions, EncodecDecodeStream, EncodecEncodeSessions, EncodecEncodeStream
 from .knn import KnnIndex, knn, knn_match
 from .metrics import STOI, MelDistance, STFTDistance, spectral_distances, stoi
@@ -10,6 +11,6 @@ from .mimi import Mimi, MimiDecodeSessions, MimiDecodeStream, MimiEncodeSessions
 from .resample import ResampleSlots, ResampleStream
 from .wavtokenizer import WavTokenizer
 
-__all__ = ["Codec", "Encodec", "EncodecEncodeStream", "EncodecDecodeStream", "EncodecEncodeSessions", "EncodecDecodeSessions", "Mimi", "MimiEncodeStream", "MimiDecodeStream", "MimiEncodeSessions", "MimiDecodeSessions", "ResampleStream", "ResampleSlots", "knn_match", "knn", "KnnIndex", "spectral_distances", "STFTDistance", "MelDistance", "stoi", "STOI", "DAC", "WavTokenizer", "WavTokenizerConfig", "WAVTOK_40", "WAVTOK_75", "WAVTOK_TINY", "EncodecConfig", "MimiConfig", "DacConfig", "ENCODEC_24KHZ", "TINY", "MIMI_24KHZ", "MIMI_TINY",
+__all__ = ["Codec", "Encodec", "EncodecEncodeStream", "EncodecDecodeStream", "EncodecEncodeSessions", "EncodecDecodeSessions", "Mimi", "MimiEncodeStream", "MimiDecodeStream", "MimiEncodeSessions", "MimiDecodeSessions", "ResampleStream", "ResampleSlots", "knn_match", "knn", "KnnIndex", "spectral_distances", "STFTDistance", "MelDistance", "stoi", "STOI", "dnsmos", "dnsmos_net", "dnsmos_segments", "DnsmosWeights", "DNSMOS", "DAC", "WavTokenizer", "WavTokenizerConfig", "WAVTOK_40", "WAVTOK_75", "WAVTOK_TINY", "EncodecConfig", "MimiConfig", "DacConfig", "ENCODEC_24KHZ", "TINY", "MIMI_24KHZ", "MIMI_TINY",
            "DAC_44KHZ", "DAC_24KHZ", "DAC_16KHZ", "DAC_TINY", "VocosConfig", "VOCOS_ENCODEC_24KHZ", "VOCOS_TINY"]
 __version__ = "0.1.0"

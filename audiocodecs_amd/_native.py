@@ -224,6 +224,16 @@ EXPORTS = {
     "ac_stoi_num_frames": (_ll, [_ll]),
     "ac_stoi_workspace_bytes": (_sz, [_i, _ll, _ll]),
     "ac_stoi": (_i, [_vp, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ac_dnsmos_source_count": (_sz, []),
+    "ac_dnsmos_source": (_i, [_vp, _sz]),
+    "ac_dnsmos_tables_bytes": (_sz, []),
+    "ac_dnsmos_tables": (_i, [_vp, _vp, _sz, _vp]),
+    "ac_dnsmos_weights_count": (_sz, []),
+    "ac_dnsmos_packed_bytes": (_sz, []),
+    "ac_dnsmos_pack": (_i, [_vp, _sz, _vp, _sz, _vp]),
+    "ac_dnsmos_workspace_bytes": (_sz, [_ll, _i, _i]),
+    "ac_dnsmos_net": (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ac_dnsmos": (_i, [_vp, _ll, _ll, _vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

@@ -229,6 +229,22 @@ class Codec(torch.nn.Module, ABC):
             hyp = hyp.narrow(-1, 0, T)
         return stoi(hyp, sig.to(hyp.dtype), self.sample_rate)
 
+    def resynthesis_dnsmos(self, sig, weights, length=None):
+        """The DNSMOS (P.808) of this codec's resynthesis of `sig` [B, T] (at `self.sample_rate`): `sig_to_toks`, `toks_to_sig`, the length
+        adjustment of downstream/test_sr.py:89-100 and `dnsmos` (dnsmos.py) of the decode -- [B].  `weights` is a `DnsmosWeights` or the path of
+        the P.808 weights.  Built from the public methods only."""
+        from .dnsmos import dnsmos
+
+        if not torch.is_tensor(sig) or sig.dim() != 2:
+            raise ValueError("`sig` must be a [B, T] tensor")
+        hyp = self.toks_to_sig(self.sig_to_toks(sig, length), length)
+        T = sig.shape[-1]
+        if T > hyp.shape[-1]:
+            hyp = torch.nn.functional.pad(hyp, [0, T - hyp.shape[-1]], mode="replicate")
+        elif T < hyp.shape[-1]:
+            hyp = hyp.narrow(-1, 0, T)
+        return dnsmos(hyp, self.sample_rate, weights)
+
     # ---- token-resampling utilities: a step-for-step restatement of /root/reference/audiocodecs/codec.py:121-180 (same RNG call order;
     #      no caller in the reference tree; SURVEY.md section 8 row f2) --------
     def resample(self, toks, p=0.2, temp=1.0, top_k=None, top_p=None):

@@ -603,6 +603,52 @@ size_t ac_stoi_workspace_bytes(int P, long long B, long long L16);
 int ac_stoi(const float* hyp_dev, const float* ref_dev, int P, long long B, long long L16, const void* tables_dev, float* score_out,
             uint8_t* kept_out, int32_t* num_segments_out, float* segments_out, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The DNSMOS P.808 score of a batch of clips at 16 kHz (handle-free): librosa's log-mel front end at the defaults
+ * the reference calls it with (n_fft 321, hop 160, periodic Hann, center = True with zero padding, power 2, 120 Slaney mel filters over
+ * 0 .. 8000 Hz with Slaney norm, (power_to_db(S, ref = max) + 40) / 40) per window of 900 frames, then the fixed P.808 net: five 3 x 3
+ * convolutions (1 -> 32 -> 32 -> 32 -> 32 -> 64, ReLU, 2 x 2 max pools behind the first, second and fourth), the global maximum and three
+ * dense layers.  The convolutions with 32 input channels run on the fp16 matrix pipe in split16 arithmetic; a window's values depend on
+ * nothing else in the call.
+ *   ac_dnsmos_source_count()     doubles of the front end's fp64 source: cos(2 pi j / 321) [321], sin [321], the filterbank [161][120].
+ *   ac_dnsmos_source             fills that source in HOST memory (pure host arithmetic in fp64; no GPU).
+ *   ac_dnsmos_tables_bytes()     bytes of the device tables (the windowed DFT basis as split16 fp16 planes, the filterbank in fp32).
+ *   ac_dnsmos_tables             one launch: builds the tables from the caller's DEVICE copy of the source.  Build once per device.
+ *   ac_dnsmos_weights_count()    floats of the net's weights as one flat fp32 array, in this order: conv5.w [32][1][3][3], conv5.b [32],
+ *                                conv6.w [32][32][3][3], conv6.b, conv7.w, conv7.b, conv8.w, conv8.b, conv9.w [64][32][3][3], conv9.b [64],
+ *                                dense3.w [64 in][64 out], dense3.b, dense4.w, dense4.b, dense5.w [64][1], dense5.b [1].
+ *   ac_dnsmos_packed_bytes()     bytes of the packed image of those weights.
+ *   ac_dnsmos_pack               one launch: packs the caller's DEVICE copy of the flat weights (fragment images of the matrix pipe, one
+ *                                power-of-two scale per output channel).  Pack once per device.
+ *   ac_dnsmos_workspace_bytes    bytes of workspace for S windows of H x W features (0 for arguments refused).  Windows are walked in
+ *                                chunks, so the bound does not grow with S beyond one chunk (32 windows at 900 x 120) plus 4 S bytes.
+ *   ac_dnsmos_net                the net alone: feats_dev [S][H][W] (H = time, W = mel; H, W >= 8, run-time values) -> score_out [S].
+ *                                Optional (may be NULL): the four stored feature maps, channels last, layer1_out [S][H/2][W/2][32],
+ *                                layer2_out and layer3_out [S][H/4][W/4][32], layer4_out [S][H/8][W/8][32], and vec_out [S][64], the global
+ *                                maxima.  Seven launches per chunk, none of them a memset node.
+ *   ac_dnsmos                    the whole call: sig_dev [B][L16]; plan_dev, int32: [S][4] = (clip, first sample, clip length, index among
+ *                                the clip's windows) of every window, the windows of a clip together and the clips in order, then
+ *                                [B][2] = (first window, number of windows >= 1) of every clip.  Sample j of a window is sample
+ *                                (first + j) mod length of its clip -- the reference doubles a short clip until it holds 9.01 s.  The host
+ *                                decides which windows exist (audiocodecs_amd.dnsmos.dnsmos_segments).  score_out [B], the mean over a
+ *                                clip's windows; optional segments_out [B][Smax] (NaN behind a clip's count) and feats_out [S][900][120].
+ *                                A window with an inf or a NaN among its samples scores NaN.  Eight launches per chunk and one at the end.
+ * AC_EINVAL for a null or misaligned pointer or a count out of range; AC_ENOMEM for a buffer or a workspace that is too short; all decided
+ * on the host before anything is launched.  Nothing allocates or synchronises.  The plan is read on the device only: entries out of range
+ * are clamped there, so no read leaves the signals. */
+size_t ac_dnsmos_source_count(void);
+int ac_dnsmos_source(double* src_host, size_t count);
+size_t ac_dnsmos_tables_bytes(void);
+int ac_dnsmos_tables(const double* src_dev, void* tables_dev, size_t tables_bytes, void* stream);
+size_t ac_dnsmos_weights_count(void);
+size_t ac_dnsmos_packed_bytes(void);
+int ac_dnsmos_pack(const float* weights_dev, size_t count, void* packed_dev, size_t packed_bytes, void* stream);
+size_t ac_dnsmos_workspace_bytes(long long S, int H, int W);
+int ac_dnsmos_net(const float* feats_dev, long long S, int H, int W, const void* packed_dev, float* score_out, float* layer1_out, float* layer2_out,
+                  float* layer3_out, float* layer4_out, float* vec_out, void* workspace_dev, size_t workspace_bytes, void* stream);
+int ac_dnsmos(const float* sig_dev, long long B, long long L16, const int32_t* plan_dev, long long S, int Smax, const void* tables_dev,
+              const void* packed_dev, float* score_out, float* segments_out, float* feats_out, void* workspace_dev, size_t workspace_bytes,
+              void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
