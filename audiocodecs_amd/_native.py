@@ -234,6 +234,10 @@ EXPORTS = {
     "ac_dnsmos_workspace_bytes": (_sz, [_ll, _i, _i]),
     "ac_dnsmos_net": (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ac_dnsmos": (_i, [_vp, _ll, _ll, _vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ac_tokstats_state_bytes": (_sz, [_i, _i]),
+    "ac_tokstats_form": (_i, [_i, _i]),
+    "ac_tokstats_accumulate": (_i, [_vp, _ll, _ll, _i, _i, _vp, _vp, _sz, _vp]),
+    "ac_tokstats_summary": (_i, [_vp, _i, _i, _vp, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

@@ -245,6 +245,36 @@ class Codec(torch.nn.Module, ABC):
             hyp = hyp.narrow(-1, 0, T)
         return dnsmos(hyp, self.sample_rate, weights)
 
+    def resynthesis_report(self, sig, length=None, dnsmos_weights=None, codebook_util=None):
+        """The recipe's numbers for a batch from ONE encode and ONE decode (downstream/test_sr.py:83-112): `sig_to_toks`, `toks_to_sig`, the
+        length adjustment of test_sr.py:89-100 once, then `spectral_distances`, `stoi` and, with `dnsmos_weights` (a `DnsmosWeights` or the
+        path of the P.808 weights), `dnsmos` of the decode; a `CodebookUtil` (tokstats.py) passed as `codebook_util` gets the tokens
+        appended with `length`.  Returns {"toks" [B, N, K], "stft" [B], "mel" [B], "stoi" [B]} and "dnsmos" [B] when weights were given:
+        what `resynthesis_distances`, `resynthesis_stoi` and `resynthesis_dnsmos` return, which encode and decode once each.  Built from
+        the public methods only."""
+        from .metrics import spectral_distances, stoi
+
+        if not torch.is_tensor(sig) or sig.dim() != 2:
+            raise ValueError("`sig` must be a [B, T] tensor")
+        toks = self.sig_to_toks(sig, length)
+        hyp = self.toks_to_sig(toks, length)
+        T = sig.shape[-1]
+        if T > hyp.shape[-1]:
+            hyp = torch.nn.functional.pad(hyp, [0, T - hyp.shape[-1]], mode="replicate")
+        elif T < hyp.shape[-1]:
+            hyp = hyp.narrow(-1, 0, T)
+        ref = sig.to(hyp.dtype)
+        report = {"toks": toks}
+        report["stft"], report["mel"] = spectral_distances(hyp, ref, self.sample_rate)
+        report["stoi"] = stoi(hyp, ref, self.sample_rate)
+        if dnsmos_weights is not None:
+            from .dnsmos import dnsmos
+
+            report["dnsmos"] = dnsmos(hyp, self.sample_rate, dnsmos_weights)
+        if codebook_util is not None:
+            codebook_util.append(toks, length)
+        return report
+
     # ---- token-resampling utilities: a step-for-step restatement of /root/reference/audiocodecs/codec.py:121-180 (same RNG call order;
     #      no caller in the reference tree; SURVEY.md section 8 row f2) --------
     def resample(self, toks, p=0.2, temp=1.0, top_k=None, top_p=None):

@@ -12,7 +12,9 @@
 //                   the above and reaches the FIR through the public ac_resample
 //   dnsmos.hip      the fused DNSMOS P.808 score (dnsmos.h): its kernels, the tables' fp64 source and the handle-free ac_dnsmos_* entry points;
 //                   includes nothing of the above
-//   ac_api.hip     the extern "C" entry points of include/audiocodecs_amd.h
+//   tokstats.hip    the token histogram and the codebook utilisation summary (tokstats.h) and the handle-free ac_tokstats_* entry points;
+//                   includes nothing of the above
+//   ac_api.hip    the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
 #include <hip/hip_runtime.h>

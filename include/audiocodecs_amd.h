@@ -649,6 +649,32 @@ int ac_dnsmos(const float* sig_dev, long long B, long long L16, const int32_t* p
               const void* packed_dev, float* score_out, float* segments_out, float* feats_out, void* workspace_dev, size_t workspace_bytes,
               void* stream);
 
+/* Token histogram and codebook utilisation (handle-free): downstream/metrics/codebook_util.py without its B == 1,
+ * its unique() per codebook and its 2 K host copies per clip.  The caller owns the state, ONE 8-byte aligned device buffer of int64 words,
+ *     counts [K][C], total, bad:   counts[k][c] the times id c was seen in codebook k, total the frames counted, bad the ids outside
+ *     [0, C) among the counted frames (they are not counted in `counts`, never index anything and never fault),
+ * and zeroes it before the first call; calls accumulate.  1 <= K <= 64, 2 <= C <= 2^20, B N K <= 2^40.  Counts are exact integers.
+ *   ac_tokstats_state_bytes(K, C)  bytes of the state, (K C + 2) * 8 (0 for a K or a C out of range).
+ *   ac_tokstats_form(K, C)         which of the two forms a call takes, a pure function of (K, C): G >= 1, the tiled form -- a workgroup keeps
+ *                                  the histogram of G = min(K, 16384 / C) codebooks in LDS and flushes its non-zero bins with 64-bit atomic
+ *                                  adds; with G < K the groups of codebooks are a grid dimension -- or 0, the direct form for C > 16384: one
+ *                                  64-bit global atomic add per token.  AC_EINVAL for a K or a C out of range.
+ *   ac_tokstats_accumulate         one launch on `stream`: one pass over toks_dev [B][N][K] (int64, contiguous, K fastest).  nvalid_dev [B]
+ *                                  (int32) may be NULL: every frame of every clip; otherwise the frames n >= nvalid[b] of clip b are skipped.
+ *                                  B == 0 or N == 0 launches nothing and returns 0.
+ *   ac_tokstats_summary            one launch, one workgroup per codebook: out_dev [K][4] doubles = (valid, entropy, util, norm_entropy) --
+ *                                  valid the non-zero bins, entropy = -sum p log2 p over p = counts / total > 0, util = valid / C and
+ *                                  norm_entropy = entropy / log2(valid) where valid > 1, else both 0 (codebook_util.py:54-70, in fp64 and in a
+ *                                  fixed order).  total == 0 gives zeros, never a NaN.
+ * AC_EINVAL for a null or misaligned pointer or a count out of range; AC_ENOMEM for a state that is too short; all decided on the host
+ * before anything is launched.  Nothing allocates, synchronises or is read back, and no launch is sized by what the device computed: both
+ * calls can be captured into a graph. */
+size_t ac_tokstats_state_bytes(int K, int C);
+int ac_tokstats_form(int K, int C);
+int ac_tokstats_accumulate(const int64_t* toks_dev, long long B, long long N, int K, int C, const int32_t* nvalid_dev, void* state_dev,
+                           size_t state_bytes, void* stream);
+int ac_tokstats_summary(const void* state_dev, int K, int C, double* out_dev, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
