@@ -157,6 +157,7 @@ static int mstream_linear(ac_handle* h, hipStream_t st, const PackedGemm& g, con
 // x [B*T][H] in place, as transformer_fwd, with the attention of mstream_attn_kernel.  `skinny`: the linear layers through
 // mstream_linear (the decode stream's choice; the encode stream passes false and keeps the tap-GEMM route bit for bit).
 // B is the dense row count of the push: every activation is [B][T]; only the positions and the rings ([Ls.B] streams) go through `slot`.
+// Test hook (ac_debug_capture): per layer the rotated qkv, the attention's output and the layer's output, as stream-ordered copies.
 static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const MStreamLayout& Ls, const int* slot, const std::vector<MimiTfLayer>& layers,
                                bool skinny, float* x, int B, int T, const MStreamScratch& s) {
     const ac_mimi_config& c = h->mcfg;
@@ -190,6 +191,7 @@ static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const 
             hipLaunchKernelGGL(mstream_rope_kernel, dim3(grid_for(n)), dim3(256), 0, st, rp);
             HIPCHK(h, hipGetLastError());
         }
+        capture(h, st, Act{s.qkv, (long long)T * 3 * A, 3 * A, T, 3 * A}, B);
         {
             MStreamAttnParams ap{s.qkv, rk, rv, pos, s.att, B, T, A, c.head_dim, c.sliding_window, R, 1.0f / std::sqrt((float)c.head_dim), slot, Ls.B};
             const double keys = std::min<double>(c.sliding_window, T + R);
@@ -197,6 +199,7 @@ static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const 
             hipLaunchKernelGGL(mstream_attn_kernel, dim3(cdiv(T, 4), c.num_attention_heads, B), dim3(256), 0, st, ap);
             HIPCHK(h, hipGetLastError());
         }
+        capture(h, st, Act{s.att, (long long)T * A, A, T, A}, B);
         if (R > 0) {   // after the attention: with T >= R the new rows overwrite slots earlier queries of this push still read
             MStreamAppendParams pp{s.qkv, rk, rv, pos, B, T, A, R, slot, Ls.B};
             const long long n = (long long)B * std::min(T, R) * A;
@@ -222,6 +225,7 @@ static int mstream_transformer(ac_handle* h, hipStream_t st, char* state, const 
         em.res = x;
         em.res_rs = H;
         if ((rc = mstream_linear(h, st, L.fc2, s.hid, rows, I, x, H, em, skinny))) return rc;
+        capture(h, st, Act{x, (long long)T * H, H, T, H}, B);
     }
     return AC_OK;
 }
@@ -279,6 +283,7 @@ static int mstream_encoder(ac_handle* h, hipStream_t st, char* state, const MStr
     if ((rc = mstream_conv(h, st, m.enc_final, staged_act(stg, B, T25 + Ls.conv_P[l], m.D), c.last_kernel_size, 1, T25, Out{stream, nullptr}, B, nullptr))) return rc;
     ws.give(stg);
     ++l;
+    capture(h, st, Act{stream, (long long)T25 * c.hidden_size, c.hidden_size, T25, c.hidden_size}, B);   // test hook: the transformer's input
     MStreamScratch s{ws.take(), ws.take(), ws.take(), ws.take()};
     if ((rc = mstream_transformer(h, st, state, Ls, slot, m.enc_tf, false, stream, B, T25, s))) return rc;
     ws.give(s.ln); ws.give(s.qkv); ws.give(s.att); ws.give(s.hid);
@@ -307,6 +312,7 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
     float* qf = ws.take();
     if ((rc = mimi_rvq_decode(h, st, toks, B * F, K, qsum, qf))) return rc;
     ws.give(qsum);
+    capture(h, st, Act{qf, (long long)F * H, H, F, H}, B);   // test hook: the dequantised rows
     // up-sampler: depthwise transposed conv (k = 2 stride) on [previous input row | chunk]
     float* stg = ws.take();
     if ((rc = mstream_stage(h, st, state, Ls, slot, l, Act{qf, (long long)F * H, H, F, H}, B, stg, cap, false, true))) return rc;
@@ -322,6 +328,7 @@ static int mstream_decoder(ac_handle* h, hipStream_t st, char* state, const MStr
         HIPCHK(h, hipGetLastError());
     }
     ws.give(stg);
+    capture(h, st, Act{stream, (long long)T25 * H, H, T25, H}, B);   // test hook: the up-sampler's output, the transformer's input
     MStreamScratch s{ws.take(), ws.take(), ws.take(), ws.take()};
     if ((rc = mstream_transformer(h, st, state, Ls, slot, m.dec_tf, skinny, stream, B, T25, s))) return rc;
     ws.give(s.ln); ws.give(s.qkv); ws.give(s.att); ws.give(s.hid);

@@ -692,7 +692,14 @@ int ac_profile_end(ac_handle* h, ac_kernel_stat* out, int cap);
 /* Test hook: while armed (buf_dev != NULL), ac_encode/ac_encode_feats/ac_decode append every module
  * output -- in HF module order, standard channels-last [B][L][C] layout -- to buf_dev.
  * ac_debug_captured returns the floats appended so far (may exceed cap_floats: nothing is written
- * past the capacity).  Disarm with ac_debug_capture(h, NULL, 0). */
+ * past the capacity).  Disarm with ac_debug_capture(h, NULL, 0).
+ * A Mimi stream push (ac_mimi_stream_encode / _decode and their _slots forms) emits, while armed, the sub-layer outputs of its
+ * transformer as dense [B][T] rows, B the rows of the native call (n of a slot push), T = F * resample_stride, A = heads * head_dim:
+ *   encode:  the transformer's input [B][T][hidden];
+ *   decode:  the dequantised rows [B][F][hidden], then the up-sampler's output = the transformer's input [B][T][hidden];
+ *   then per layer, in order:  qkv [B][T][3A] (rotated q | rotated k | v),  att [B][T][A] (before o_proj),  the layer's output
+ *   [B][T][hidden].
+ * These are stream-ordered copies: the push's tokens or samples are the bits of a push without the hook. */
 int ac_debug_capture(ac_handle* h, float* buf_dev, size_t cap_floats);
 /* Developer / test switches of a handle: A/B paths whose results are EQUIVALENT (bit-identical or fp32-faithful; named in the
  * parity tests): "tap_epi_staged", "tap_dil", "tap_stagger", "tap_pick", "tap8", "tap8_form", "tap8_spread", "rb_stream",
