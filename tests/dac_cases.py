@@ -30,6 +30,43 @@ CASES = [
 ]
 
 
+def _rate_cases(tag: str, K: int, seed: int) -> list:
+    """The cases of one published model other than the 44.1 kHz one: strides (2,4,5,8), hop 320, K codebooks.  T = 2049 gives 6 frames;
+    T = 320 and T = 319 give one frame each (it decodes to 312 samples); K8 is the wrapper's default `num_codebooks`."""
+    return [
+        dict(name=f"{tag}_noise_b2", cfg=tag, weights_seed=0, kind="noise", B=2, T=2049, seed=seed, K=K, embs=True),
+        dict(name=f"{tag}_T320", cfg=tag, weights_seed=0, kind="noise", B=1, T=320, seed=seed + 1, K=K),
+        dict(name=f"{tag}_T319", cfg=tag, weights_seed=0, kind="noise", B=1, T=319, seed=seed + 2, K=K),
+        dict(name=f"{tag}_tones_K8", cfg=tag, weights_seed=0, kind="tones", B=1, T=1601, seed=seed + 3, K=8),
+        dict(name=f"{tag}_decode_rand", cfg=tag, weights_seed=0, kind="decode", B=2, N=5, K=K, seed=seed + 4),
+    ]
+
+
+# The 16 kHz and 24 kHz models (config.DAC_16KHZ: 12 codebooks, config.DAC_24KHZ: 32) at FULL width -- a list of its own, with a fixture
+# file of its own (tests/golden/dac_rates_golden.npz, `tools/make_golden_dac.py --rates`): CASES is parametrised over the session's
+# checkpoint fixture, which knows "full" and "tiny" only; the modules that use RATE_CASES build the two checkpoints themselves (rate_config).
+RATE_CASES = _rate_cases("dac16", 12, 251) + _rate_cases("dac24", 32, 261)
+
+
+def rate_config(tag: str):
+    from audiocodecs_amd.config import DAC_16KHZ, DAC_24KHZ
+
+    return {"dac16": DAC_16KHZ, "dac24": DAC_24KHZ}[tag]
+
+
+_RATE_CKPT: dict = {}
+
+
+def rate_checkpoint(tag: str):
+    """tag -> (DacConfig, synthetic HF-layout state dict, seed 0); built once per process (about 10 s of CPU per config)."""
+    if tag not in _RATE_CKPT:
+        from audiocodecs_amd import checkpoint
+
+        cfg = rate_config(tag)
+        _RATE_CKPT[tag] = (cfg, checkpoint.synthetic_dac_state_dict(cfg, seed=0))
+    return _RATE_CKPT[tag]
+
+
 def make_input(case: dict, golden_dir: str) -> dict:
     kind = case["kind"]
     if kind == "noise":

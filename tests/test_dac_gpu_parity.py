@@ -87,7 +87,12 @@ def test_every_module_output_matches_standin_hooks(name, dac_golden, codecs):
 
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_golden_fixture(case, dac_golden, codecs):
-    z, meta = dac_golden
+    check_golden_case(case, *dac_golden, codecs)
+
+
+def check_golden_case(case, z, meta, codecs):
+    """The HIP path against one case of a stand-in fixture file (z, meta); `codecs(cfg_name, weights_seed, K, latent=False)` gives the
+    wrapper.  Also the body of tests/test_dac_rates_gpu.py::test_golden_fixture."""
     name = case["name"]
     info = meta["cases"][name]
     K = info["K"]

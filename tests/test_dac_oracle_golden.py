@@ -22,9 +22,14 @@ def strided(a, meta):
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_oracle_matches_standin_fixture(case, variant, dac_golden, dac_checkpoints):
     z, meta = dac_golden
-    name = case["name"]
     cfg, sd = dac_checkpoints(case["cfg"], case["weights_seed"])
-    W = O.cast_weights(sd)
+    check_oracle_case(case, variant, z, meta, cfg, O.cast_weights(sd))
+
+
+def check_oracle_case(case, variant, z, meta, cfg, W):
+    """The oracle (fp32 weights W of config cfg) against one case of a stand-in fixture file (z, meta); also the body of
+    tests/test_dac_rates_oracle_golden.py."""
+    name = case["name"]
     inp = make_input(case, GOLDEN_DIR)
     info = meta["cases"][name]
     K = info["K"]

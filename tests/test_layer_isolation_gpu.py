@@ -173,11 +173,11 @@ def _judge(t, direction, case, got, ref64, ref32, figures, failures, named_rows=
             assert bool((err[:, r] <= tol[:, r]).all()), f"layer {t.name} ({case}): row {r}"
 
 
-def isolate(name, cfg, W, W64, direction, flat, x0, case, only=None, named_rows=(), result=None):
+def isolate(name, cfg, W, W64, direction, flat, x0, case, only=None, named_rows=(), result=None, record_as=None):
     """Walk the capture `flat` of one call: per layer, fp64 and fp32 references from the GPU's own previous tap, the bar, the two
     figures.  `only(tap)`: recompute just these layers (the others' sizes come from a dry run).  `result`: what the captured call
-    returned ([B,N,D] features or [B,T] samples, on the CPU) -- checked as the last layer, from the last tap.  Returns the failure
-    messages."""
+    returned ([B,N,D] features or [B,T] samples, on the CPU) -- checked as the last layer, from the last tap.  `record_as`: the parity
+    record's codec key where it is not `name` (a second config of the same codec).  Returns the failure messages."""
     taps = LC.taps_of(name, cfg, direction)
     f32, f64 = LC.layer_fns(name, cfg, W, direction), LC.layer_fns(name, cfg, W64, direction)
     shapes = _meta_shapes(name, cfg, W, direction, x0.shape) if only else None
@@ -211,7 +211,7 @@ def isolate(name, cfg, W, W64, direction, flat, x0, case, only=None, named_rows=
         assert result.dtype == torch.float32 and tuple(result.shape) == tuple(ref64.shape), f"{case}: result {tuple(result.shape)}, the oracle's {tuple(ref64.shape)}"
         assert bool(torch.isfinite(result).all()), f"{case}: the {direction} result is not finite"
         _judge(t, direction, case, result, ref64, ref32, figures, failures)
-    parity_record.record(name, f"layer_isolation/{case}/{direction}", per_layer=figures)
+    parity_record.record(record_as or name, f"layer_isolation/{case}/{direction}", per_layer=figures)
     return failures
 
 

@@ -3,7 +3,8 @@ arrangement and epilogue every conv / linear layer of the four codecs gets.  Out
 kernel runs, so the GPU tests cannot see a layer moving to another kernel; this table can.
 
 The layer cases are the tap-GEMM launches of bench.py's default workloads (EnCodec / WavTokenizer 64 clips, Mimi 128, DAC 256;
-10 s each) and of one 10 s clip, as run_tap saw them; each expected value is the profile record ac_profile_end reports for that
+10 s each) and of one 10 s clip, as run_tap saw them, plus those of the 16 kHz DAC model ("dac16": 64 clips and one clip of 10 s; its
+stride-5 conv, K2560 J2 s5, and stride-5 transposed conv, N1920, are layers no other codec here has); each expected value is the profile record ac_profile_end reports for that
 launch with the handle switch "prof_detail" on: the route's name and run_tap's shape suffix.  The switch cases come from the same
 kind of runs with one developer switch set; the edge cases (exact products, misaligned operands, nine taps) follow run_tap's rules."""
 import ctypes as C
@@ -276,6 +277,84 @@ LAYERS = [
     ("dac B1", layer(1, 220416, 192, [seg(220416, 192, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2, dil> B1 M220416 N192 K1344 J7 s1 d3", 0),
     ("dac B1", layer(1, 220416, 192, [seg(220416, 192, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2, dil> B1 M220416 N192 K1344 J7 s1 d9", 0),
     ("dac B1", layer(1, 220417, 192, [seg(220416, 192, J=2)], alpha=1, y_bs=42319872, y_elu=1, y_len=42319872, y_off=-96), "tap_gemm6_kernel<2, 2, 2, 3, 2> B1 M220417 N192 K384 J2 s1", 0),
+    # dac16 B64 (config.DAC_16KHZ, strides (2,4,5,8), 64 clips x 10 s)
+    ("dac16 B64", layer(64, 160000, 64, [seg(160000, 64, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 1, 2> B64 M160000 N64 K448 J7 s1", DIRECT),
+    ("dac16 B64", layer(64, 160000, 64, [seg(160000, 64)], alpha=1, res=1, res_rs=64, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 1, 2> B64 M160000 N64 K64 J1 s1", DIRECT),
+    ("dac16 B64", layer(64, 160000, 64, [seg(160000, 64, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 1, 2> B64 M160000 N64 K448 J7 s1 d3", DIRECT),
+    ("dac16 B64", layer(64, 160000, 64, [seg(160000, 64, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 1, 2> B64 M160000 N64 K448 J7 s1 d9", DIRECT),
+    ("dac16 B64", layer(64, 80000, 128, [seg(160000, 64, J=2, pad=1, s=2)], alpha=1, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B64 M80000 N128 K256 J2 s2", 0),
+    ("dac16 B64", layer(64, 80000, 128, [seg(80000, 128, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B64 M80000 N128 K896 J7 s1", 0),
+    ("dac16 B64", layer(64, 80000, 128, [seg(80000, 128)], alpha=1, res=1, res_rs=128, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B64 M80000 N128 K128 J1 s1", 0),
+    ("dac16 B64", layer(64, 80000, 128, [seg(80000, 128, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B64 M80000 N128 K896 J7 s1 d3", 0),
+    ("dac16 B64", layer(64, 80000, 128, [seg(80000, 128, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B64 M80000 N128 K896 J7 s1 d9", 0),
+    ("dac16 B64", layer(64, 20000, 256, [seg(80000, 128, J=2, pad=2, s=4)], alpha=1, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M20000 N256 K1024 J2 s4", 0),
+    ("dac16 B64", layer(64, 20000, 256, [seg(20000, 256, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M20000 N256 K1792 J7 s1", 0),
+    ("dac16 B64", layer(64, 20000, 256, [seg(20000, 256)], alpha=1, res=1, res_rs=256, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M20000 N256 K256 J1 s1", 0),
+    ("dac16 B64", layer(64, 20000, 256, [seg(20000, 256, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 2, 2, dil> B64 M20000 N256 K1792 J7 s1 d3", 0),
+    ("dac16 B64", layer(64, 20000, 256, [seg(20000, 256, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 2, 2, dil> B64 M20000 N256 K1792 J7 s1 d9", 0),
+    ("dac16 B64", layer(64, 4000, 512, [seg(20000, 256, J=2, pad=3, s=5)], alpha=1, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M4000 N512 K2560 J2 s5", 0),
+    ("dac16 B64", layer(64, 4000, 512, [seg(4000, 512, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M4000 N512 K3584 J7 s1", 0),
+    ("dac16 B64", layer(64, 4000, 512, [seg(4000, 512)], alpha=1, res=1, res_rs=512, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M4000 N512 K512 J1 s1", 0),
+    ("dac16 B64", layer(64, 4000, 512, [seg(4000, 512, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 2, 2, dil> B64 M4000 N512 K3584 J7 s1 d3", 0),
+    ("dac16 B64", layer(64, 4000, 512, [seg(4000, 512, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 2, 2, dil> B64 M4000 N512 K3584 J7 s1 d9", 0),
+    ("dac16 B64", layer(64, 500, 1024, [seg(4000, 512, J=2, pad=4, s=8)], alpha=1, y=0, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M500 N1024 K8192 J2 s8", 0),
+    ("dac16 B64", layer(64, 500, 1024, [seg(500, 1024, J=3, pad=1)]), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M500 N1024 K3072 J3 s1", DIRECT),
+    ("dac16 B64", layer(64, 500, 1536, [seg(500, 1024, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M500 N1536 K7168 J7 s1", 0),
+    ("dac16 B64", layer(64, 501, 6144, [seg(500, 1536, J=2)], alpha=1, y_bs=3072000, y_elu=1, y_len=3072000, y_off=-3072), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M501 N6144 K3072 J2 s1", 0),
+    ("dac16 B64", layer(64, 4000, 768, [seg(4000, 768, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M4000 N768 K5376 J7 s1", 0),
+    ("dac16 B64", layer(64, 4000, 768, [seg(4000, 768)], alpha=1, res=1, res_rs=768, y_elu=1), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M4000 N768 K768 J1 s1", 0),
+    ("dac16 B64", layer(64, 4000, 768, [seg(4000, 768, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 2, 2, dil> B64 M4000 N768 K5376 J7 s1 d3", 0),
+    ("dac16 B64", layer(64, 4000, 768, [seg(4000, 768, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 2, 2, dil> B64 M4000 N768 K5376 J7 s1 d9", 0),
+    ("dac16 B64", layer(64, 4001, 1920, [seg(4000, 768, J=2)], alpha=1, y_bs=7679616, y_elu=1, y_len=7679616, y_off=-1152), "tap_gemm6_kernel<1, 4, 4, 1, 2> B64 M4001 N1920 K1536 J2 s1", 0),
+    ("dac16 B64", layer(64, 19999, 384, [seg(19999, 384, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B64 M19999 N384 K2688 J7 s1", 0),
+    ("dac16 B64", layer(64, 19999, 384, [seg(19999, 384)], alpha=1, res=1, res_rs=384, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B64 M19999 N384 K384 J1 s1", 0),
+    ("dac16 B64", layer(64, 19999, 384, [seg(19999, 384, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2, dil> B64 M19999 N384 K2688 J7 s1 d3", 0),
+    ("dac16 B64", layer(64, 19999, 384, [seg(19999, 384, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2, dil> B64 M19999 N384 K2688 J7 s1 d9", 0),
+    ("dac16 B64", layer(64, 20000, 768, [seg(19999, 384, J=2)], alpha=1, y_bs=15359232, y_elu=1, y_len=15359232, y_off=-384), "tap_gemm8_kernel<2, 4, 4, 2, 2> B64 M20000 N768 K768 J2 s1", 0),
+    ("dac16 B64", layer(64, 79996, 192, [seg(79996, 192, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2> B64 M79996 N192 K1344 J7 s1", 0),
+    ("dac16 B64", layer(64, 79996, 192, [seg(79996, 192)], alpha=1, res=1, res_rs=192, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2> B64 M79996 N192 K192 J1 s1", 0),
+    ("dac16 B64", layer(64, 79996, 192, [seg(79996, 192, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2, dil> B64 M79996 N192 K1344 J7 s1 d3", 0),
+    ("dac16 B64", layer(64, 79996, 192, [seg(79996, 192, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2, dil> B64 M79996 N192 K1344 J7 s1 d9", 0),
+    ("dac16 B64", layer(64, 79997, 192, [seg(79996, 192, J=2)], alpha=1, y_bs=15359232, y_elu=1, y_len=15359232, y_off=-96), "tap_gemm6_kernel<2, 2, 2, 3, 2> B64 M79997 N192 K384 J2 s1", 0),
+    # dac16 B1
+    ("dac16 B1", layer(1, 160000, 64, [seg(160000, 64, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 1, 2> B1 M160000 N64 K448 J7 s1", DIRECT),
+    ("dac16 B1", layer(1, 160000, 64, [seg(160000, 64)], alpha=1, res=1, res_rs=64, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 1, 2> B1 M160000 N64 K64 J1 s1", DIRECT),
+    ("dac16 B1", layer(1, 160000, 64, [seg(160000, 64, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 1, 2> B1 M160000 N64 K448 J7 s1 d3", DIRECT),
+    ("dac16 B1", layer(1, 160000, 64, [seg(160000, 64, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 1, 2> B1 M160000 N64 K448 J7 s1 d9", DIRECT),
+    ("dac16 B1", layer(1, 80000, 128, [seg(160000, 64, J=2, pad=1, s=2)], alpha=1, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M80000 N128 K256 J2 s2", 0),
+    ("dac16 B1", layer(1, 80000, 128, [seg(80000, 128, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M80000 N128 K896 J7 s1", 0),
+    ("dac16 B1", layer(1, 80000, 128, [seg(80000, 128)], alpha=1, res=1, res_rs=128, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M80000 N128 K128 J1 s1", 0),
+    ("dac16 B1", layer(1, 80000, 128, [seg(80000, 128, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M80000 N128 K896 J7 s1 d3", 0),
+    ("dac16 B1", layer(1, 80000, 128, [seg(80000, 128, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M80000 N128 K896 J7 s1 d9", 0),
+    ("dac16 B1", layer(1, 20000, 256, [seg(80000, 128, J=2, pad=2, s=4)], alpha=1, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M20000 N256 K1024 J2 s4", 0),
+    ("dac16 B1", layer(1, 20000, 256, [seg(20000, 256, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M20000 N256 K1792 J7 s1", 0),
+    ("dac16 B1", layer(1, 20000, 256, [seg(20000, 256)], alpha=1, res=1, res_rs=256, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M20000 N256 K256 J1 s1", 0),
+    ("dac16 B1", layer(1, 20000, 256, [seg(20000, 256, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M20000 N256 K1792 J7 s1 d3", 0),
+    ("dac16 B1", layer(1, 20000, 256, [seg(20000, 256, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M20000 N256 K1792 J7 s1 d9", 0),
+    ("dac16 B1", layer(1, 4000, 512, [seg(20000, 256, J=2, pad=3, s=5)], alpha=1, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N512 K2560 J2 s5", 0),
+    ("dac16 B1", layer(1, 4000, 512, [seg(4000, 512, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N512 K3584 J7 s1", 0),
+    ("dac16 B1", layer(1, 4000, 512, [seg(4000, 512)], alpha=1, res=1, res_rs=512, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N512 K512 J1 s1", 0),
+    ("dac16 B1", layer(1, 4000, 512, [seg(4000, 512, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N512 K3584 J7 s1 d3", 0),
+    ("dac16 B1", layer(1, 4000, 512, [seg(4000, 512, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N512 K3584 J7 s1 d9", 0),
+    ("dac16 B1", layer(1, 500, 1024, [seg(4000, 512, J=2, pad=4, s=8)], alpha=1, y=0, y_elu=1), "tap_gemm8_kernel<2, 4, 2, 2, 2> B1 M500 N1024 K8192 J2 s8", SPREAD),
+    ("dac16 B1", layer(1, 500, 1024, [seg(500, 1024, J=3, pad=1)]), "tap_gemm8_kernel<2, 4, 2, 2, 2> B1 M500 N1024 K3072 J3 s1", DIRECT | SPREAD),
+    ("dac16 B1", layer(1, 500, 1536, [seg(500, 1024, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm8_kernel<2, 4, 2, 2, 2> B1 M500 N1536 K7168 J7 s1", SPREAD),
+    ("dac16 B1", layer(1, 501, 6144, [seg(500, 1536, J=2)], alpha=1, y_bs=3072000, y_elu=1, y_len=3072000, y_off=-3072), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M501 N6144 K3072 J2 s1", 0),
+    ("dac16 B1", layer(1, 4000, 768, [seg(4000, 768, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N768 K5376 J7 s1", 0),
+    ("dac16 B1", layer(1, 4000, 768, [seg(4000, 768)], alpha=1, res=1, res_rs=768, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N768 K768 J1 s1", 0),
+    ("dac16 B1", layer(1, 4000, 768, [seg(4000, 768, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N768 K5376 J7 s1 d3", 0),
+    ("dac16 B1", layer(1, 4000, 768, [seg(4000, 768, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 8, 4, 1, 2> B1 M4000 N768 K5376 J7 s1 d9", 0),
+    ("dac16 B1", layer(1, 4001, 1920, [seg(4000, 768, J=2)], alpha=1, y_bs=7679616, y_elu=1, y_len=7679616, y_off=-1152), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M4001 N1920 K1536 J2 s1", 0),
+    ("dac16 B1", layer(1, 19999, 384, [seg(19999, 384, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M19999 N384 K2688 J7 s1", 0),
+    ("dac16 B1", layer(1, 19999, 384, [seg(19999, 384)], alpha=1, res=1, res_rs=384, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M19999 N384 K384 J1 s1", 0),
+    ("dac16 B1", layer(1, 19999, 384, [seg(19999, 384, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2, dil> B1 M19999 N384 K2688 J7 s1 d3", 0),
+    ("dac16 B1", layer(1, 19999, 384, [seg(19999, 384, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<1, 4, 4, 1, 2, dil> B1 M19999 N384 K2688 J7 s1 d9", 0),
+    ("dac16 B1", layer(1, 20000, 768, [seg(19999, 384, J=2)], alpha=1, y_bs=15359232, y_elu=1, y_len=15359232, y_off=-384), "tap_gemm8_kernel<2, 4, 4, 2, 2> B1 M20000 N768 K768 J2 s1", 0),
+    ("dac16 B1", layer(1, 79996, 192, [seg(79996, 192, J=7, pad=3)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2> B1 M79996 N192 K1344 J7 s1", 0),
+    ("dac16 B1", layer(1, 79996, 192, [seg(79996, 192)], alpha=1, res=1, res_rs=192, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2> B1 M79996 N192 K192 J1 s1", 0),
+    ("dac16 B1", layer(1, 79996, 192, [seg(79996, 192, J=7, dil=3, pad=9)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2, dil> B1 M79996 N192 K1344 J7 s1 d3", 0),
+    ("dac16 B1", layer(1, 79996, 192, [seg(79996, 192, J=7, dil=9, pad=27)], alpha=1, y=0, y_elu=1), "tap_gemm6_kernel<2, 2, 2, 3, 2, dil> B1 M79996 N192 K1344 J7 s1 d9", 0),
+    ("dac16 B1", layer(1, 79997, 192, [seg(79996, 192, J=2)], alpha=1, y_bs=15359232, y_elu=1, y_len=15359232, y_off=-96), "tap_gemm6_kernel<2, 2, 2, 3, 2> B1 M79997 N192 K384 J2 s1", 0),
     # wavtokenizer B1
     ("wavtokenizer B1", layer(1, 60000, 64, [seg(240000, 32, J=2, lim=240002, pad=2, s=4)]), "tap_gemm6_kernel<2, 2, 2, 1, 2> B1 M60000 N64 K256 J2 s4", 0),
     ("wavtokenizer B1", layer(1, 12000, 128, [seg(60000, 64, J=2, lim=60002, pad=3, s=5)]), "tap_gemm6_kernel<1, 4, 4, 1, 2> B1 M12000 N128 K640 J2 s5", DIRECT),

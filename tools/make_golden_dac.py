@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Generate tests/golden/dac_golden.npz from the STAND-IN for the reference's DAC backend.
 
-    python tools/make_golden_dac.py
+    python tools/make_golden_dac.py            # dac_cases.CASES      -> tests/golden/dac_golden.npz (44.1 kHz and tiny)
+    python tools/make_golden_dac.py --rates    # dac_cases.RATE_CASES -> tests/golden/dac_rates_golden.npz (16 kHz and 24 kHz, full width)
+
+The two modes write one file each and never the other's.
 
 `audiocodecs.dac.DAC` (/root/reference/audiocodecs/dac.py) cannot be imported here: its backend
 `descript-audio-codec` is not installed (dac.py:44-48 raises ImportError).  What runs instead is the
@@ -27,12 +30,16 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from audiocodecs_amd import checkpoint  # noqa: E402
-from audiocodecs_amd.config import DAC_44KHZ, DAC_TINY  # noqa: E402
-from dac_cases import CASES, REC_STRIDE, make_input  # noqa: E402
+from audiocodecs_amd.config import DAC_16KHZ, DAC_24KHZ, DAC_44KHZ, DAC_TINY  # noqa: E402
+from dac_cases import CASES, RATE_CASES, REC_STRIDE, make_input  # noqa: E402
 from oracle import dac_oracle as O  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 ACT_FULL_MAX, ACT_STRIDE, EMBS_STRIDE = 16384, 13, 499
+# --rates: the projected tables are [12 | 32, 1024, 1024]; every 4999th entry (a prime: every table, code range and column is visited)
+# keeps the file in the tens of kilobytes.  The stride travels in the file's meta, as EMBS_STRIDE does.
+RATES_EMBS_STRIDE = 4999
+CONFIGS = {"full": DAC_44KHZ, "tiny": DAC_TINY, "dac16": DAC_16KHZ, "dac24": DAC_24KHZ}
 
 
 def hf_config(cfg):
@@ -46,7 +53,7 @@ def hf_config(cfg):
     )
 
 
-def main():
+def main(cases=CASES, file_name="dac_golden.npz", embs_stride=EMBS_STRIDE):
     import transformers
     from transformers import DacModel
 
@@ -55,13 +62,13 @@ def main():
     meta = {
         "transformers": transformers.__version__, "torch": torch.__version__,
         "source": "STAND-IN transformers.DacModel called as audiocodecs/dac.py calls dac.DAC (descript-audio-codec absent)",
-        "rec_stride": REC_STRIDE, "act_full_max": ACT_FULL_MAX, "act_stride": ACT_STRIDE, "embs_stride": EMBS_STRIDE,
+        "rec_stride": REC_STRIDE, "act_full_max": ACT_FULL_MAX, "act_stride": ACT_STRIDE, "embs_stride": embs_stride,
         "cases": {},
     }
     models = {}
-    for case in CASES:
+    for case in cases:
         name, cfg_name, seed = case["name"], case["cfg"], case["weights_seed"]
-        cfg = {"full": DAC_44KHZ, "tiny": DAC_TINY}[cfg_name]
+        cfg = CONFIGS[cfg_name]
         key = (cfg_name, seed)
         if key not in models:
             sd = checkpoint.synthetic_dac_state_dict(cfg, seed=seed)
@@ -110,11 +117,11 @@ def main():
                     a = v.numpy().reshape(-1)
                     out[f"{name}.act.{nm}"] = a[:: (1 if a.size <= ACT_FULL_MAX else ACT_STRIDE)].copy()
                     info.setdefault("act_shapes", {})[nm] = list(v.shape)
-            if name in ("full_noise_b2", "tiny_taps"):
+            if name in ("full_noise_b2", "tiny_taps") or case.get("embs"):
                 cbs = torch.stack([q.codebook.weight for q in m.quantizer.quantizers[:K]])
                 proj = torch.stack([q.out_proj(q.codebook.weight[:, :, None])[..., 0] for q in m.quantizer.quantizers[:K]])
-                out[f"{name}.embs_latent_strided"] = cbs.numpy().reshape(-1)[::EMBS_STRIDE].copy()
-                out[f"{name}.embs_proj_strided"] = proj.numpy().reshape(-1)[::EMBS_STRIDE].copy()
+                out[f"{name}.embs_latent_strided"] = cbs.numpy().reshape(-1)[::embs_stride].copy()
+                out[f"{name}.embs_proj_strided"] = proj.numpy().reshape(-1)[::embs_stride].copy()
                 info["embs_shapes"] = [list(cbs.shape), list(proj.shape)]
         rec_np = rec.numpy()
         out[f"{name}.rec_strided"] = rec_np.reshape(-1)[::REC_STRIDE].copy()
@@ -126,10 +133,15 @@ def main():
         print(name, {k: v for k, v in info.items() if k != "act_shapes"}, flush=True)
 
     out["meta_json"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
-    path = os.path.join(GOLD, "dac_golden.npz")
+    path = os.path.join(GOLD, file_name)
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path) / 1e6, "MB")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--rates"]:
+        main(RATE_CASES, "dac_rates_golden.npz", RATES_EMBS_STRIDE)
+    elif not sys.argv[1:]:
+        main()
+    else:
+        sys.exit(__doc__)
