@@ -197,20 +197,27 @@ class Codec(torch.nn.Module, ABC):
         matching_set = torch.cat([self.sig_to_feats(s[None] if s.dim() == 1 else s).flatten(end_dim=-2) for s in spk_sigs])
         return self.feats_to_sig(knn_match(self.toks_to_qfeats(toks), matching_set, topk))
 
+    def _resynthesize(self, sig, length):
+        """`sig_to_toks`, `toks_to_sig` and the length adjustment of downstream/test_sr.py:89-100 (the decode is replicate-padded or narrowed
+        to the input's length): (toks [B, N, K], hyp [B, T])."""
+        if not torch.is_tensor(sig) or sig.dim() != 2:
+            raise ValueError("`sig` must be a [B, T] tensor")
+        toks = self.sig_to_toks(sig, length)
+        hyp = self.toks_to_sig(toks, length)
+        T = sig.shape[-1]
+        if T > hyp.shape[-1]:
+            hyp = torch.nn.functional.pad(hyp, [0, T - hyp.shape[-1]], mode="replicate")
+        elif T < hyp.shape[-1]:
+            hyp = hyp.narrow(-1, 0, T)
+        return toks, hyp
+
     def resynthesis_distances(self, sig, length=None):
         """The STFT and mel spectral distances of this codec's resynthesis of `sig` [B, T] (at `self.sample_rate`) against `sig` itself:
         `sig_to_toks`, `toks_to_sig`, the length adjustment of downstream/test_sr.py:89-100 (the decode is replicate-padded or narrowed to
         the input's length) and `spectral_distances` (metrics.py) -- (stft [B], mel [B]).  Built from the public methods only."""
         from .metrics import spectral_distances
 
-        if not torch.is_tensor(sig) or sig.dim() != 2:
-            raise ValueError("`sig` must be a [B, T] tensor")
-        hyp = self.toks_to_sig(self.sig_to_toks(sig, length), length)
-        T = sig.shape[-1]
-        if T > hyp.shape[-1]:
-            hyp = torch.nn.functional.pad(hyp, [0, T - hyp.shape[-1]], mode="replicate")
-        elif T < hyp.shape[-1]:
-            hyp = hyp.narrow(-1, 0, T)
+        hyp = self._resynthesize(sig, length)[1]      # (the tokens go here, before the metric allocates)
         return spectral_distances(hyp, sig.to(hyp.dtype), self.sample_rate)
 
     def resynthesis_stoi(self, sig, length=None):
@@ -219,14 +226,7 @@ class Codec(torch.nn.Module, ABC):
         the public methods only."""
         from .metrics import stoi
 
-        if not torch.is_tensor(sig) or sig.dim() != 2:
-            raise ValueError("`sig` must be a [B, T] tensor")
-        hyp = self.toks_to_sig(self.sig_to_toks(sig, length), length)
-        T = sig.shape[-1]
-        if T > hyp.shape[-1]:
-            hyp = torch.nn.functional.pad(hyp, [0, T - hyp.shape[-1]], mode="replicate")
-        elif T < hyp.shape[-1]:
-            hyp = hyp.narrow(-1, 0, T)
+        hyp = self._resynthesize(sig, length)[1]      # (the tokens go here, before the metric allocates)
         return stoi(hyp, sig.to(hyp.dtype), self.sample_rate)
 
     def resynthesis_dnsmos(self, sig, weights, length=None):
@@ -235,14 +235,7 @@ class Codec(torch.nn.Module, ABC):
         the P.808 weights.  Built from the public methods only."""
         from .dnsmos import dnsmos
 
-        if not torch.is_tensor(sig) or sig.dim() != 2:
-            raise ValueError("`sig` must be a [B, T] tensor")
-        hyp = self.toks_to_sig(self.sig_to_toks(sig, length), length)
-        T = sig.shape[-1]
-        if T > hyp.shape[-1]:
-            hyp = torch.nn.functional.pad(hyp, [0, T - hyp.shape[-1]], mode="replicate")
-        elif T < hyp.shape[-1]:
-            hyp = hyp.narrow(-1, 0, T)
+        hyp = self._resynthesize(sig, length)[1]      # (the tokens go here, before the metric allocates)
         return dnsmos(hyp, self.sample_rate, weights)
 
     def resynthesis_report(self, sig, length=None, dnsmos_weights=None, codebook_util=None):
@@ -254,15 +247,7 @@ class Codec(torch.nn.Module, ABC):
         the public methods only."""
         from .metrics import spectral_distances, stoi
 
-        if not torch.is_tensor(sig) or sig.dim() != 2:
-            raise ValueError("`sig` must be a [B, T] tensor")
-        toks = self.sig_to_toks(sig, length)
-        hyp = self.toks_to_sig(toks, length)
-        T = sig.shape[-1]
-        if T > hyp.shape[-1]:
-            hyp = torch.nn.functional.pad(hyp, [0, T - hyp.shape[-1]], mode="replicate")
-        elif T < hyp.shape[-1]:
-            hyp = hyp.narrow(-1, 0, T)
+        toks, hyp = self._resynthesize(sig, length)
         ref = sig.to(hyp.dtype)
         report = {"toks": toks}
         report["stft"], report["mel"] = spectral_distances(hyp, ref, self.sample_rate)

@@ -126,12 +126,6 @@ struct DmMeanParams {
     int B, Smax, S;
 };
 
-__device__ __forceinline__ void dm_split64(double v, _Float16& hi, _Float16& lo) {
-    const double s = v * 16384.0;
-    hi = (_Float16)(float)s;
-    lo = (_Float16)(float)(s - (double)(float)hi);
-}
-
 // Clears the chunk's maxima: a kernel of the library's own, not hipMemsetAsync -- a memset node captured into a hipGraph does not replay
 // reliably on this runtime (split16_kernels.h).
 __global__ __launch_bounds__(256) void dm_clear_kernel(unsigned* words, int n) {
@@ -157,7 +151,7 @@ __global__ __launch_bounds__(256) void dm_tables_kernel(const DmTablesParams p) 
                 v = 0.5 * (1.0 - p.src[n]) * p.src[(qc & 1) ? DM_NFFT + j : j];
             }
             _Float16 h, l;
-            dm_split64(v, h, l);
+            s16_split64(v, h, l);
             hi[e] = h;
             lo[e] = l;
         }

@@ -4,13 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include "audiocodecs_amd.h"
+#include "metric_host.h"
 #include "dnsmos.h"
 
 namespace ac {
-
-static bool dm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool dm_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 // librosa.filters.mel(sr = 16000, n_fft = 321, n_mels = 120, fmin = 0, fmax = 8000, htk = False, norm = "slaney"), restated (DESIGN.md 8l:
 // unpinned against librosa; pinned against transformers' mel_filter_bank by the tests): Slaney's scale is linear below 1 kHz (200 / 3 Hz
@@ -25,16 +22,10 @@ static double dm_mel_to_hz(double m) {
 }
 static void dm_filterbank(double* fb) {
     const double m_max = dm_hz_to_mel(8000.0);
-    double f_pts[DM_MELS + 2];
+    double f_pts[DM_MELS + 2], f_bin[DM_BINS];
     for (int i = 0; i < DM_MELS + 2; ++i) f_pts[i] = dm_mel_to_hz(m_max * i / (DM_MELS + 1));
-    for (int k = 0; k < DM_BINS; ++k) {
-        const double f = k * 16000.0 / DM_NFFT;
-        for (int m = 0; m < DM_MELS; ++m) {
-            const double down = (f - f_pts[m]) / (f_pts[m + 1] - f_pts[m]), up = (f_pts[m + 2] - f) / (f_pts[m + 2] - f_pts[m + 1]);
-            const double v = down < up ? down : up;
-            fb[k * DM_MELS + m] = v > 0.0 ? v * 2.0 / (f_pts[m + 2] - f_pts[m]) : 0.0;
-        }
-    }
+    for (int k = 0; k < DM_BINS; ++k) f_bin[k] = k * 16000.0 / DM_NFFT;
+    triangle_filterbank(fb, f_pts, DM_MELS, f_bin, DM_BINS, true);
 }
 
 struct DmShape {
@@ -54,21 +45,20 @@ static bool dm_shape(long long S, int H, int W, DmShape& g) {
     if (g.chunk > S) g.chunk = S;
     return true;
 }
-static size_t dm_up(size_t n) { return (n + 255) & ~(size_t)255; }
-// workspace: [slots: smax C, gmax C x 64][scores S][melpow C H W][a1][a2][a3][a4]
+// workspace, every piece 256-byte aligned: [slots: smax C, gmax C x 64][scores S][melpow C H W][a1][a2][a3][a4]
 struct DmLayout {
     size_t slots, scores, melpow, a[4], total;
 };
 static DmLayout dm_layout(long long S, const DmShape& g) {
     DmLayout l;
     const size_t C = (size_t)g.chunk;
-    size_t o = 0;
-    l.slots = o, o += dm_up(C * 65 * 4);
-    l.scores = o, o += dm_up((size_t)S * 4);
-    l.melpow = o, o += dm_up(C * g.H[0] * g.W[0] * 4);
+    WorkspaceCursor<256> ws;
+    l.slots = ws.take(C * 65 * 4);
+    l.scores = ws.take((size_t)S * 4);
+    l.melpow = ws.take(C * g.H[0] * g.W[0] * 4);
     const int li[4] = {1, 2, 2, 3};
-    for (int i = 0; i < 4; ++i) l.a[i] = o, o += dm_up(C * g.H[li[i]] * g.W[li[i]] * 32 * 4);
-    l.total = o;
+    for (int i = 0; i < 4; ++i) l.a[i] = ws.take(C * g.H[li[i]] * g.W[li[i]] * 32 * 4);
+    l.total = ws.at;
     return l;
 }
 
@@ -138,26 +128,26 @@ int ac_dnsmos_source(double* src_host, size_t count) {
 size_t ac_dnsmos_tables_bytes(void) { return (size_t)DM_BASIS_HALVES * 2 + (size_t)DM_BINS * DM_MELS * 4 + 2 * DM_MELS * 4; }
 
 int ac_dnsmos_tables(const double* src_dev, void* tables_dev, size_t tables_bytes, void* stream) {
-    if (!src_dev || !tables_dev || !dm_aligned16(src_dev) || !dm_aligned16(tables_dev)) return AC_EINVAL;
+    if (!src_dev || !tables_dev || !aligned<16>(src_dev) || !aligned<16>(tables_dev)) return AC_EINVAL;
     if (tables_bytes < ac_dnsmos_tables_bytes()) return AC_ENOMEM;
     _Float16* basis = reinterpret_cast<_Float16*>(tables_dev);
     float* fb = reinterpret_cast<float*>(basis + DM_BASIS_HALVES);
     const DmTablesParams p{src_dev, basis, fb, reinterpret_cast<int*>(fb + DM_BINS * DM_MELS)};
     const long long threads = (long long)DM_PASSES * DM_KS * 4 * 64 + (long long)DM_BINS * DM_MELS + DM_MELS;
     hipLaunchKernelGGL(dm_tables_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 size_t ac_dnsmos_weights_count(void) { return DM_W_COUNT; }
 size_t ac_dnsmos_packed_bytes(void) { return DM_PK_BYTES; }
 
 int ac_dnsmos_pack(const float* weights_dev, size_t count, void* packed_dev, size_t packed_bytes, void* stream) {
-    if (!weights_dev || !packed_dev || !dm_aligned4(weights_dev) || !dm_aligned16(packed_dev) || count != (size_t)DM_W_COUNT) return AC_EINVAL;
+    if (!weights_dev || !packed_dev || !aligned<4>(weights_dev) || !aligned<16>(packed_dev) || count != (size_t)DM_W_COUNT) return AC_EINVAL;
     if (packed_bytes < DM_PK_BYTES) return AC_ENOMEM;
     const DmPackParams p{weights_dev, reinterpret_cast<unsigned char*>(packed_dev)};
     const int threads = 5 * 9 * 2 * 64 + 320 + 4160 + 4160 + 65;
     hipLaunchKernelGGL(dm_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 size_t ac_dnsmos_workspace_bytes(long long S, int H, int W) {
@@ -169,8 +159,8 @@ size_t ac_dnsmos_workspace_bytes(long long S, int H, int W) {
 int ac_dnsmos_net(const float* feats_dev, long long S, int H, int W, const void* packed_dev, float* score_out, float* layer1_out, float* layer2_out, float* layer3_out,
                   float* layer4_out, float* vec_out, void* workspace_dev, size_t workspace_bytes, void* stream) {
     if (!feats_dev || !packed_dev || !score_out || !workspace_dev) return AC_EINVAL;
-    if (!dm_aligned4(feats_dev) || !dm_aligned16(packed_dev) || !dm_aligned4(score_out) || !dm_aligned16(layer1_out) || !dm_aligned16(layer2_out) ||
-        !dm_aligned16(layer3_out) || !dm_aligned16(layer4_out) || !dm_aligned4(vec_out) || !dm_aligned16(workspace_dev))
+    if (!aligned<4>(feats_dev) || !aligned<16>(packed_dev) || !aligned<4>(score_out) || !aligned<16>(layer1_out) || !aligned<16>(layer2_out) ||
+        !aligned<16>(layer3_out) || !aligned<16>(layer4_out) || !aligned<4>(vec_out) || !aligned<16>(workspace_dev))
         return AC_EINVAL;
     DmShape g;
     if (!dm_shape(S, H, W, g)) return AC_EINVAL;
@@ -184,14 +174,14 @@ int ac_dnsmos_net(const float* feats_dev, long long S, int H, int W, const void*
         dm_clear(ws + l.slots, g, st);
         dm_net_chunk(a, g, l, ws, reinterpret_cast<const unsigned char*>(packed_dev), c0, C, st);
     }
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 int ac_dnsmos(const float* sig_dev, long long B, long long L16, const int32_t* plan_dev, long long S, int Smax, const void* tables_dev, const void* packed_dev,
               float* score_out, float* segments_out, float* feats_out, void* workspace_dev, size_t workspace_bytes, void* stream) {
     if (!sig_dev || !plan_dev || !tables_dev || !packed_dev || !score_out || !workspace_dev) return AC_EINVAL;
-    if (!dm_aligned4(sig_dev) || !dm_aligned16(plan_dev) || !dm_aligned16(tables_dev) || !dm_aligned16(packed_dev) || !dm_aligned4(score_out) ||
-        !dm_aligned4(segments_out) || !dm_aligned4(feats_out) || !dm_aligned16(workspace_dev))
+    if (!aligned<4>(sig_dev) || !aligned<16>(plan_dev) || !aligned<16>(tables_dev) || !aligned<16>(packed_dev) || !aligned<4>(score_out) ||
+        !aligned<4>(segments_out) || !aligned<4>(feats_out) || !aligned<16>(workspace_dev))
         return AC_EINVAL;
     DmShape g;
     if (B < 1 || B > S || L16 < 1 || L16 > DM_MAX_L || Smax < 1 || Smax > S || !dm_shape(S, DM_FRAMES, DM_MELS, g)) return AC_EINVAL;
@@ -213,7 +203,7 @@ int ac_dnsmos(const float* sig_dev, long long B, long long L16, const int32_t* p
     }
     const DmMeanParams m{seg, plan_dev + 4 * S, score_out, segments_out, (int)B, Smax, (int)S};
     hipLaunchKernelGGL(dm_mean_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, m);
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // ac_knn_* entry points.  Every refusal is decided here on the host, before anything is launched; nothing allocates or synchronises.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "audiocodecs_amd.h"
+#include "metric_host.h"
 #include "knn.h"
 
 namespace ac {
@@ -12,7 +12,6 @@ static bool knn_rows_ok(long long n) { return n >= 1 && n <= KNN_MAX_ROWS; }
 static long long knn_mpad(long long M) { return (M + 15) / 16 * 16; }
 static int knn_ms(int H) { return H == 512 ? 1 : 2; }                 // row tiles per wave (registers: two tile sets of H = 512 leave room for one)
 static int knn_kl(int topk) { return topk <= 4 ? 4 : 8; }
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Slices of the table for a call that names none: enough workgroups (one wave each) for the 1024 SIMDs, while a slice keeps at least 8
 // tiles (a wave's prologue -- 16 MS rows normalised and split -- and its 16-lane merge stay small beside its walk) and the finish kernel
@@ -46,13 +45,13 @@ size_t ac_knn_packed_bytes(long long M, int H) {
 }
 
 int ac_knn_pack(const float* set_dev, long long M, int H, void* packed_dev, size_t packed_bytes, void* stream) {
-    if (!set_dev || !packed_dev || !aligned16(set_dev) || !aligned16(packed_dev) || !knn_rows_ok(M) || !knn_width_ok(H)) return AC_EINVAL;
+    if (!set_dev || !packed_dev || !aligned<16>(set_dev) || !aligned<16>(packed_dev) || !knn_rows_ok(M) || !knn_width_ok(H)) return AC_EINVAL;
     if (packed_bytes < ac_knn_packed_bytes(M, H)) return AC_ENOMEM;
     const long long Mpad = knn_mpad(M);
     _Float16* image = reinterpret_cast<_Float16*>(packed_dev);
     const KnnPackParams p{set_dev, image, reinterpret_cast<unsigned*>(image + Mpad * H * 2), (int)M, H};
     hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)(Mpad / 16)), dim3(64), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 int ac_knn_num_splits(long long Q, long long M, int H, int num_splits) {
@@ -68,8 +67,8 @@ size_t ac_knn_workspace_bytes(long long Q, long long M, int H, int topk, int num
 
 int ac_knn_match(const float* query_dev, long long Q, const float* set_dev, const void* packed_dev, long long M, int H, int topk, int num_splits,
                  float* out_dev, int64_t* idx_dev, float* sim_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-    if (!query_dev || !set_dev || !packed_dev || !workspace_dev || !aligned16(query_dev) || !aligned16(set_dev) || !aligned16(packed_dev) ||
-        !aligned16(workspace_dev) || (out_dev && !aligned16(out_dev)))
+    if (!query_dev || !set_dev || !packed_dev || !workspace_dev || !aligned<16>(query_dev) || !aligned<16>(set_dev) || !aligned<16>(packed_dev) ||
+        !aligned<16>(workspace_dev) || !aligned<16>(out_dev))
         return AC_EINVAL;
     if (topk < 1 || topk > KNN_MAX_TOPK) return AC_EINVAL;
     const int S = ac_knn_num_splits(Q, M, H, num_splits);
@@ -92,7 +91,7 @@ int ac_knn_match(const float* query_dev, long long Q, const float* set_dev, cons
     const KnnFinishParams f{set_dev, ws_sim, ws_idx, out_dev, reinterpret_cast<long long*>(idx_dev), sim_dev, (int)Q, H, S, topk};
     if (KL == 4) hipLaunchKernelGGL(knn_finish_kernel<4>, dim3((unsigned)Q), dim3(64), 0, st, f);
     else hipLaunchKernelGGL(knn_finish_kernel<8>, dim3((unsigned)Q), dim3(64), 0, st, f);
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 }  // extern "C"

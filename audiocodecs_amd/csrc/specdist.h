@@ -71,13 +71,6 @@ struct SdFinishParams {
     int F;
 };
 
-// v 2^14 as an fp16 pair.  hi need not be the nearest fp16 (the conversion may round twice): lo takes whatever it leaves.
-__device__ __forceinline__ void sd_split64(double v, _Float16& hi, _Float16& lo) {
-    const double s = v * 16384.0;
-    hi = (_Float16)(float)s;
-    lo = (_Float16)(float)(s - (double)(float)hi);
-}
-
 // One thread per (fragment, lane) of either table: 8 values, both planes.
 __global__ __launch_bounds__(256) void sd_tables_kernel(const SdTablesParams p) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -95,7 +88,7 @@ __global__ __launch_bounds__(256) void sd_tables_kernel(const SdTablesParams p) 
             const double w = 0.5 * (1.0 - p.src[n]);
             const double v = bin < SD_BINS ? w * p.src[(qc & 1) ? ((j + 768) & 1023) : j] : 0.0;      // sin a = cos(a - pi / 2)
             _Float16 h, l;
-            sd_split64(v, h, l);
+            s16_split64(v, h, l);
             hi[e] = h;
             lo[e] = l;
         }
@@ -111,7 +104,7 @@ __global__ __launch_bounds__(256) void sd_tables_kernel(const SdTablesParams p) 
             const int bin = 32 * pass + 16 * (e >> 2) + 4 * kq + (e & 3);
             const double v = bin < SD_BINS ? p.src[SD_NFFT + bin * SD_MELS + 16 * mt + i] : 0.0;
             _Float16 h, l;
-            sd_split64(v, h, l);
+            s16_split64(v, h, l);
             hi[e] = h;
             lo[e] = l;
         }

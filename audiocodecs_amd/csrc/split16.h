@@ -115,6 +115,14 @@ __device__ __forceinline__ float fma_pinned(float a, float b, float acc) {
     return acc;
 }
 
+// an fp64 table value v 2^14 as an fp16 pair (the metrics' table kernels: values of at most 1 under s16_exponent(bits of 1.0f) = 14).
+// hi need not be the nearest fp16 (the conversion may round twice): lo takes whatever it leaves.
+__device__ __forceinline__ void s16_split64(double v, _Float16& hi, _Float16& lo) {
+    const double s = v * 16384.0;
+    hi = (_Float16)(float)s;
+    lo = (_Float16)(float)(s - (double)(float)hi);
+}
+
 // 4 fp32 values x scale -> hi / lo fp16 planes, 8 bytes each at element offset `o` (planes `plane` elements apart):
 //   hi = fp16(v s),  lo = fp16(fma(v, s, -hi))   -- v_fma_mixlo/mixhi_f16 does the fma on the fp16 `hi` and the rounding of the
 // result in ONE instruction: two instructions per value in all (v_pk_mul, v_cvt_pk, 2 x v_fma_mix per pair)

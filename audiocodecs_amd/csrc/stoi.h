@@ -103,13 +103,6 @@ struct StFinishParams {
     int B, NS0;
 };
 
-// v 2^14 as an fp16 pair (hi need not be the nearest fp16: lo takes whatever it leaves)
-__device__ __forceinline__ void st_split64(double v, _Float16& hi, _Float16& lo) {
-    const double s = v * 16384.0;
-    hi = (_Float16)(float)s;
-    lo = (_Float16)(float)(s - (double)(float)hi);
-}
-
 __global__ __launch_bounds__(256) void stoi_tables_kernel(const StTablesParams p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int nb = ST_TILES * ST_KS * 2 * 64;
@@ -124,7 +117,7 @@ __global__ __launch_bounds__(256) void stoi_tables_kernel(const StTablesParams p
             const int j = (bin * n) & (ST_NFFT - 1);
             const double v = live ? p.src[n] * p.src[ST_WIN + (c ? ((j + 384) & (ST_NFFT - 1)) : j)] : 0.0;      // sin a = cos(a - pi / 2)
             _Float16 h, l;
-            st_split64(v, h, l);
+            s16_split64(v, h, l);
             hi[e] = h;
             lo[e] = l;
         }

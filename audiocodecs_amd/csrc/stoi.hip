@@ -4,14 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include "audiocodecs_amd.h"
+#include "metric_host.h"
 #include "stoi.h"
 
 namespace ac {
 
-static bool st_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool st_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-static size_t st_pad16(size_t n) { return (n + 15) / 16 * 16; }
 static long long st_len10(long long L16) { return (ST_UP * L16 + ST_DOWN - 1) / ST_DOWN; }
 static long long st_frames(long long L16) { return (st_len10(L16) - ST_WIN) / ST_HOP + 1; }
 static bool st_shape_ok(int P, long long B, long long L16) {
@@ -29,16 +26,16 @@ static StLayout st_layout(int P, long long B, long long L16) {
     l.L10 = st_len10(L16);
     l.F0 = st_frames(L16);
     l.NS0 = l.F0 > ST_SEG ? l.F0 - ST_SEG : 0;
-    size_t o = 0;
-    l.x10 = o;    o += st_pad16((size_t)(1 + P) * B * l.L10 * sizeof(float));
-    l.energy = o; o += st_pad16((size_t)B * l.F0 * sizeof(float));
-    l.src = o;    o += st_pad16((size_t)B * l.F0 * sizeof(int));
-    l.kept = o;   o += st_pad16((size_t)B * l.F0);
-    l.K = o;      o += st_pad16((size_t)B * sizeof(int));
-    l.bad = o;    o += st_pad16((size_t)(1 + P) * B * sizeof(int));
-    l.env = o;    o += st_pad16((size_t)(1 + P) * B * l.F0 * 16 * sizeof(float));
-    l.segsum = o; o += st_pad16((size_t)P * B * l.NS0 * sizeof(float));
-    l.total = o;
+    WorkspaceCursor<16> ws;
+    l.x10 = ws.take((size_t)(1 + P) * B * l.L10 * sizeof(float));
+    l.energy = ws.take((size_t)B * l.F0 * sizeof(float));
+    l.src = ws.take((size_t)B * l.F0 * sizeof(int));
+    l.kept = ws.take((size_t)B * l.F0);
+    l.K = ws.take((size_t)B * sizeof(int));
+    l.bad = ws.take((size_t)(1 + P) * B * sizeof(int));
+    l.env = ws.take((size_t)(1 + P) * B * l.F0 * 16 * sizeof(float));
+    l.segsum = ws.take((size_t)P * B * l.NS0 * sizeof(float));
+    l.total = ws.at;
     return l;
 }
 
@@ -51,15 +48,6 @@ static double st_i0(double x) {
         sum += term;
     }
     return sum;
-}
-
-// cos(2 pi j / 512) with the argument reduced to the first octant as an integer: exact at the multiples of a quarter turn
-static double st_cos512(int j) {
-    j &= 511;
-    const int q = j >> 7, r = j & 127;
-    const double u = M_PI / 256.0;
-    const double cs = r <= 64 ? cos(r * u) : sin((128 - r) * u), sn = r <= 64 ? sin(r * u) : cos((128 - r) * u);
-    return q == 0 ? cs : q == 1 ? -sn : q == 2 ? -cs : sn;
 }
 
 // pystoi's resample_oct(x, 10000, 16000) filter (restated: DESIGN.md 8k, unpinned): Kaiser-windowed sinc, 60 dB, roll-off fc / 10, normalised
@@ -91,7 +79,7 @@ int ac_stoi_source(double* src_host, size_t count) {
     if (!src_host) return AC_EINVAL;
     if (count < (size_t)ST_SRC_COUNT) return AC_ENOMEM;
     for (int n = 0; n < ST_WIN; ++n) src_host[n] = 0.5 * (1.0 - cos(2.0 * M_PI * (n + 1) / (ST_WIN + 1)));      // hanning(258)[1:-1]
-    for (int j = 0; j < ST_NFFT; ++j) src_host[ST_WIN + j] = st_cos512(j);
+    for (int j = 0; j < ST_NFFT; ++j) src_host[ST_WIN + j] = cos_turn(j, ST_NFFT);
     st_fir(src_host + ST_WIN + ST_NFFT);
     return AC_OK;
 }
@@ -99,13 +87,13 @@ int ac_stoi_source(double* src_host, size_t count) {
 size_t ac_stoi_tables_bytes(void) { return ST_WINDOW_BYTES + ST_FIR_BYTES + (size_t)ST_BASIS_HALVES * sizeof(_Float16); }
 
 int ac_stoi_tables(const double* src_dev, void* tables_dev, size_t tables_bytes, void* stream) {
-    if (!src_dev || !tables_dev || !st_aligned16(src_dev) || !st_aligned16(tables_dev)) return AC_EINVAL;
+    if (!src_dev || !tables_dev || !aligned<16>(src_dev) || !aligned<16>(tables_dev)) return AC_EINVAL;
     if (tables_bytes < ac_stoi_tables_bytes()) return AC_ENOMEM;
     char* t = reinterpret_cast<char*>(tables_dev);
     const StTablesParams p{src_dev, reinterpret_cast<float*>(t), reinterpret_cast<float*>(t + ST_WINDOW_BYTES), reinterpret_cast<_Float16*>(t + ST_WINDOW_BYTES + ST_FIR_BYTES)};
     const int threads = ST_TILES * ST_KS * 2 * 64 + ST_WIN + ST_UP * ST_FIR_TAPS;
     hipLaunchKernelGGL(stoi_tables_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 long long ac_stoi_num_frames(long long L16) { return L16 >= 1 && L16 <= ST_MAX_L16 && st_len10(L16) >= ST_WIN ? st_frames(L16) : 0; }
@@ -115,8 +103,8 @@ size_t ac_stoi_workspace_bytes(int P, long long B, long long L16) { return st_sh
 int ac_stoi(const float* hyp_dev, const float* ref_dev, int P, long long B, long long L16, const void* tables_dev, float* score_out, uint8_t* kept_out,
             int32_t* num_segments_out, float* segments_out, void* workspace_dev, size_t workspace_bytes, void* stream) {
     if (!hyp_dev || !ref_dev || !tables_dev || !score_out || !workspace_dev) return AC_EINVAL;
-    if (!st_aligned4(hyp_dev) || !st_aligned4(ref_dev) || !st_aligned16(tables_dev) || !st_aligned16(workspace_dev) || !st_aligned4(score_out) ||
-        !st_aligned4(num_segments_out) || !st_aligned4(segments_out))
+    if (!aligned<4>(hyp_dev) || !aligned<4>(ref_dev) || !aligned<16>(tables_dev) || !aligned<16>(workspace_dev) || !aligned<4>(score_out) ||
+        !aligned<4>(num_segments_out) || !aligned<4>(segments_out))
         return AC_EINVAL;
     if (!st_shape_ok(P, B, L16)) return AC_EINVAL;
     const StLayout l = st_layout(P, B, L16);
@@ -155,7 +143,7 @@ int ac_stoi(const float* hyp_dev, const float* ref_dev, int P, long long B, long
     }
     const StFinishParams fp{segsum, K, bad, score_out, segments_out, iB, NS0};
     hipLaunchKernelGGL(stoi_finish_kernel, dim3((unsigned)(P * B)), dim3(64), 0, st, fp);
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 }  // extern "C"

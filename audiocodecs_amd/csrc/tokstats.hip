@@ -3,13 +3,12 @@
 // nothing allocates or synchronises.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "audiocodecs_amd.h"
+#include "metric_host.h"
 #include "tokstats.h"
 
 namespace ac {
 
 static bool ts_shape_ok(int K, int C) { return K >= 1 && K <= TS_MAX_K && C >= TS_MIN_C && C <= TS_MAX_C; }
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 // workgroups along x: one per 4096 elements, at most 1024 (tokstats.h: what keeps a private bin from wrapping)
 static unsigned ts_blocks(long long E) {
@@ -35,10 +34,10 @@ int ac_tokstats_form(int K, int C) {
 
 int ac_tokstats_accumulate(const int64_t* toks_dev, long long B, long long N, int K, int C, const int32_t* nvalid_dev, void* state_dev,
                            size_t state_bytes, void* stream) {
-    if (!ts_shape_ok(K, C) || B < 0 || N < 0 || !state_dev || !aligned8(state_dev)) return AC_EINVAL;
+    if (!ts_shape_ok(K, C) || B < 0 || N < 0 || !state_dev || !aligned<8>(state_dev)) return AC_EINVAL;
     if (state_bytes < ac_tokstats_state_bytes(K, C)) return AC_ENOMEM;
     if (B == 0 || N == 0) return AC_OK;
-    if (!toks_dev || !aligned8(toks_dev) || (nvalid_dev && (reinterpret_cast<uintptr_t>(nvalid_dev) & 3))) return AC_EINVAL;
+    if (!toks_dev || !aligned<8>(toks_dev) || !aligned<4>(nvalid_dev)) return AC_EINVAL;
     if (B > TS_MAX_ELEMS / N || B * N > TS_MAX_ELEMS / K) return AC_EINVAL;
     const long long E = B * N * K;
     unsigned long long* counts = reinterpret_cast<unsigned long long*>(state_dev);
@@ -56,14 +55,14 @@ int ac_tokstats_accumulate(const int64_t* toks_dev, long long B, long long N, in
         if (small) hipLaunchKernelGGL(tokstats_direct_kernel<unsigned>, grid, dim3(TS_BLOCK), 0, st, p);
         else hipLaunchKernelGGL(tokstats_direct_kernel<unsigned long long>, grid, dim3(TS_BLOCK), 0, st, p);
     }
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 int ac_tokstats_summary(const void* state_dev, int K, int C, double* out_dev, void* stream) {
-    if (!ts_shape_ok(K, C) || !state_dev || !out_dev || !aligned8(state_dev) || !aligned8(out_dev)) return AC_EINVAL;
+    if (!ts_shape_ok(K, C) || !state_dev || !out_dev || !aligned<8>(state_dev) || !aligned<8>(out_dev)) return AC_EINVAL;
     const unsigned long long* counts = reinterpret_cast<const unsigned long long*>(state_dev);
     hipLaunchKernelGGL(tokstats_summary_kernel, dim3((unsigned)K), dim3(TS_BLOCK), 0, (hipStream_t)stream, counts, counts + (size_t)K * C, C, out_dev);
-    return hipGetLastError() == hipSuccess ? AC_OK : AC_EHIP;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -24,24 +24,24 @@ is pinned to ``torch.stft``, the filterbank to ``transformers.audio_utils.mel_fi
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict
 
 import numpy as np
 import torch
 
-from .metrics import _DistanceStats, _resampled_len
+from . import _metric_host as _host
+from . import _native
+from ._metric_host import SAMPLE_RATE
+from .metrics import _DistanceStats
 
 __all__ = ["dnsmos", "dnsmos_net", "dnsmos_segments", "load_weights", "read_onnx", "weights_from_onnx", "DnsmosWeights", "DNSMOS", "SAMPLE_RATE", "INPUT_LENGTH",
            "WINDOW", "FRAMES", "N_MELS", "WEIGHT_SHAPES"]
 
-SAMPLE_RATE = 16000
 INPUT_LENGTH = 9.01
 WINDOW = int(INPUT_LENGTH * SAMPLE_RATE)      # 144160 samples make a window; its first 144000 feed the features
 FRAMES = 900
 N_MELS = 120
-MAX_LEN = 1 << 24
 
 # the 16 tensors, in the order of the library's flat array (include/audiocodecs_amd.h ac_dnsmos_weights_count)
 WEIGHT_SHAPES = {
@@ -229,9 +229,7 @@ class DnsmosWeights:
         return torch.cat([self.tensors[k].reshape(-1) for k in WEIGHT_SHAPES])
 
     def packed(self, device: torch.device) -> torch.Tensor:
-        from . import _native
-
-        idx = device.index if device.index is not None else torch.cuda.current_device()
+        idx = _host.device_index(device)
         if idx not in self._packed:
             L = _native.lib()
             flat = self.flat()
@@ -242,7 +240,7 @@ class DnsmosWeights:
                 dev = torch.device("cuda", idx)
                 flat_dev = flat.to(dev)
                 packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                rc = L.ac_dnsmos_pack(C.c_void_p(flat_dev.data_ptr()), flat.numel(), C.c_void_p(packed.data_ptr()), nbytes, _native._stream())
+                rc = L.ac_dnsmos_pack(_native._ptr(flat_dev), flat.numel(), _native._ptr(packed), nbytes, _native._stream())
                 _native.check(rc, None, "ac_dnsmos_pack")
                 torch.cuda.current_stream().synchronize()      # (once per device: flat_dev may go, and other streams may use the image)
             self._packed[idx] = packed
@@ -293,28 +291,7 @@ def _plan(lengths):
     return torch.tensor(wins + clips, dtype=torch.int32), len(wins) // 4, max(clips[1::2])
 
 
-_TABLES: Dict[int, torch.Tensor] = {}
 _PLANS: Dict[tuple, tuple] = {}      # (device, B, L16) -> the plan of a call without `lens`, on the device
-
-
-def _tables(device: torch.device) -> torch.Tensor:
-    """The windowed DFT basis (split16 planes) and the Slaney filterbank, built once per device from the library's fp64 source."""
-    from . import _native
-
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _TABLES:
-        L = _native.lib()
-        n = L.ac_dnsmos_source_count()
-        src = torch.empty(n, dtype=torch.float64)
-        _native.check(L.ac_dnsmos_source(C.c_void_p(src.data_ptr()), n), None, "ac_dnsmos_source")
-        nbytes = L.ac_dnsmos_tables_bytes()
-        with torch.cuda.device(idx):
-            src_dev = src.to(torch.device("cuda", idx))
-            tables = torch.empty(nbytes, dtype=torch.uint8, device=src_dev.device)
-            _native.check(L.ac_dnsmos_tables(C.c_void_p(src_dev.data_ptr()), C.c_void_p(tables.data_ptr()), nbytes, _native._stream()), None, "ac_dnsmos_tables")
-            torch.cuda.current_stream().synchronize()
-        _TABLES[idx] = tables
-    return _TABLES[idx]
 
 
 def _weights(weights) -> DnsmosWeights:
@@ -331,8 +308,6 @@ def dnsmos_net(feats: torch.Tensor, weights, return_layers: bool = False):
     """feats [S, H, W] (H = time, W = mel; H, W >= 8) -> the P.808 net's score [S] fp32.  With `return_layers` (score, layers, vec): the four
     feature maps the net stores, as [S, 32, h, w] views of channels-last memory (behind the first, second and fourth convolution's pool and
     behind the third convolution), and vec [S, 64], the global maxima behind the fifth."""
-    from . import _native
-
     weights = _weights(weights)
     if not torch.is_tensor(feats) or feats.dim() != 3:
         raise ValueError("`feats` must be a [S, H, W] tensor")
@@ -344,21 +319,16 @@ def dnsmos_net(feats: torch.Tensor, weights, return_layers: bool = False):
     if S == 0:
         score = torch.empty(0, dtype=torch.float32, device=dev)
         return (score, [torch.empty(0, 32, h, w, dtype=torch.float32, device=dev) for h, w in sizes], torch.empty(0, 64, dtype=torch.float32, device=dev)) if return_layers else score
-    if not feats.is_cuda:
-        raise _native.NativeError("audiocodecs_amd.dnsmos runs on MI355X only: move the features to a cuda device (there is deliberately no CPU fallback)")
-    L = _native.lib()
+    _host.need_cuda(feats.is_cuda, "dnsmos", "features")
     packed = weights.packed(dev)
     x = feats.detach().to(torch.float32).contiguous()
     score = torch.empty(S, dtype=torch.float32, device=dev)
     layers = [torch.empty(S, h, w, 32, dtype=torch.float32, device=dev) for h, w in sizes] if return_layers else [None] * 4
     vec = torch.empty(S, 64, dtype=torch.float32, device=dev) if return_layers else None
-    nws = L.ac_dnsmos_workspace_bytes(S, H, W)
-    if nws == 0:
-        raise ValueError(f"ac_dnsmos_workspace_bytes refuses S={S}, H={H}, W={W}")
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    ws = _host.sized_buffer("ac_dnsmos_workspace_bytes", dev, S=S, H=H, W=W)
+    ptr = _native._ptr
     with torch.cuda.device(dev):
-        rc = L.ac_dnsmos_net(C.c_void_p(x.data_ptr()), S, H, W, C.c_void_p(packed.data_ptr()), C.c_void_p(score.data_ptr()), *(_native._ptr(t) for t in layers),
-                             _native._ptr(vec), C.c_void_p(ws.data_ptr()), nws, _native._stream())
+        rc = _native.lib().ac_dnsmos_net(ptr(x), S, H, W, ptr(packed), ptr(score), *(ptr(t) for t in layers), ptr(vec), ptr(ws), ws.numel(), _native._stream())
     _native.check(rc, None, "ac_dnsmos_net")
     if return_layers:
         return score, [t.permute(0, 3, 1, 2) for t in layers], vec
@@ -367,16 +337,13 @@ def dnsmos_net(feats: torch.Tensor, weights, return_layers: bool = False):
 
 def _check_args(sig, sample_rate, lens):
     """Everything that can be refused without a GPU.  Returns (B, T, L16)."""
-    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate < 1:
-        raise ValueError(f"`sample_rate` ({sample_rate!r}) must be a positive int")
+    _host.check_sample_rate(sample_rate)
     if not torch.is_tensor(sig) or sig.dim() != 2:
         raise ValueError("`sig` must be a [B, T] tensor")
     B, T = (int(n) for n in sig.shape)
     if lens is not None and (not torch.is_tensor(lens) or tuple(lens.shape) != (B,)):
         raise ValueError(f"`lens` must be a [B] tensor of relative lengths (B = {B})")
-    L16 = _resampled_len(T, sample_rate)
-    if L16 > MAX_LEN:
-        raise ValueError(f"signals of {L16} samples at {SAMPLE_RATE} Hz are longer than the {MAX_LEN} a call takes: split them")
+    L16 = _host.resampled_len(T, sample_rate)
     if L16 < 1:
         raise ValueError("a clip of 0 samples has no window (the reference would double it forever)")
     return B, T, L16
@@ -403,7 +370,6 @@ def dnsmos(sig: torch.Tensor, sample_rate: int, weights, lens=None, return_segme
     and costs one host read; without it the call reads nothing back and can be captured in a graph.  With `return_segments`
     (score, segments, feats): segments [B, Smax] the windows' scores, NaN past a clip's count; feats [S, 900, 120] the log-mel features
     of all windows, clip after clip.  A clip that holds an inf or a NaN scores NaN and disturbs no other clip."""
-    from . import _native
     from .resample import resample
 
     weights = _weights(weights)
@@ -413,8 +379,7 @@ def dnsmos(sig: torch.Tensor, sample_rate: int, weights, lens=None, return_segme
         score = torch.empty(0, dtype=torch.float32, device=dev)
         return (score, torch.empty(0, 0, dtype=torch.float32, device=dev), torch.empty(0, FRAMES, N_MELS, dtype=torch.float32, device=dev)) if return_segments else score
     lengths = _lengths(lens, B, L16)
-    if not sig.is_cuda:
-        raise _native.NativeError("audiocodecs_amd.dnsmos runs on MI355X only: move the signal to a cuda device (there is deliberately no CPU fallback)")
+    _host.need_cuda(sig.is_cuda, "dnsmos", "signal")
     x = resample(sig.detach().to(torch.float32), sample_rate, SAMPLE_RATE).contiguous()
     assert int(x.shape[1]) == L16
     key = (dev.index, B, L16)
@@ -427,18 +392,14 @@ def dnsmos(sig: torch.Tensor, sample_rate: int, weights, lens=None, return_segme
             if len(_PLANS) >= 64:
                 _PLANS.clear()
             _PLANS[key] = (plan, S, Smax)
-    L = _native.lib()
-    tables, packed = _tables(dev), weights.packed(dev)
+    tables, packed = _host.tables("dnsmos", dev), weights.packed(dev)
     score = torch.empty(B, dtype=torch.float32, device=dev)
     segs = torch.empty(B, Smax, dtype=torch.float32, device=dev) if return_segments else None
     feats = torch.empty(S, FRAMES, N_MELS, dtype=torch.float32, device=dev) if return_segments else None
-    nws = L.ac_dnsmos_workspace_bytes(S, FRAMES, N_MELS)
-    if nws == 0:
-        raise ValueError(f"ac_dnsmos_workspace_bytes refuses S={S}")
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    ws = _host.sized_buffer("ac_dnsmos_workspace_bytes", dev, FRAMES, N_MELS, S=S)
+    ptr = _native._ptr
     with torch.cuda.device(dev):
-        rc = L.ac_dnsmos(C.c_void_p(x.data_ptr()), B, L16, C.c_void_p(plan.data_ptr()), S, Smax, C.c_void_p(tables.data_ptr()), C.c_void_p(packed.data_ptr()),
-                         C.c_void_p(score.data_ptr()), _native._ptr(segs), _native._ptr(feats), C.c_void_p(ws.data_ptr()), nws, _native._stream())
+        rc = _native.lib().ac_dnsmos(ptr(x), B, L16, ptr(plan), S, Smax, ptr(tables), ptr(packed), ptr(score), ptr(segs), ptr(feats), ptr(ws), ws.numel(), _native._stream())
     _native.check(rc, None, "ac_dnsmos")
     return (score, segs, feats) if return_segments else score
 
@@ -463,9 +424,4 @@ class DNSMOS(_DistanceStats):
         """`lens` is honoured, as the reference honours it for this metric alone."""
         if not torch.is_tensor(sig) or sig.dim() != 2:
             raise ValueError("`sig` must be a [B, T] tensor")
-        ids = list(ids)
-        if len(ids) != sig.shape[0]:
-            raise ValueError(f"{len(ids)} ids for {sig.shape[0]} clips")
-        scores = dnsmos(sig, self.sample_rate, self.model, lens=lens)
-        self.ids += ids
-        self.scores += scores.cpu().tolist()
+        self._record(ids, sig.shape[0], lambda: dnsmos(sig, self.sample_rate, self.model, lens=lens))

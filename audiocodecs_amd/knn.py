@@ -16,9 +16,10 @@ yields NaN distances and arbitrary picks).  Equal computed similarities go to th
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
+
+from . import _metric_host as _host
+from . import _native
 
 __all__ = ["knn_match", "knn", "KnnIndex", "auto_splits", "WIDTHS", "MAX_TOPK"]
 
@@ -50,8 +51,6 @@ def _check_splits(num_splits) -> int:
 def auto_splits(Q: int, M: int, H: int) -> int:
     """The number of slices of the matching set a match of Q rows against M rows of width H walks side by side when the caller names
     none (``ac_knn_num_splits``: pure host arithmetic, needs no GPU)."""
-    from . import _native
-
     s = _native.lib().ac_knn_num_splits(int(Q), int(M), _padded_width(int(H)), 0)
     if s < 1:
         raise ValueError(f"auto_splits: bad arguments (Q={Q}, M={M}, H={H})")
@@ -63,8 +62,6 @@ class KnnIndex:
     order): build once per target speaker, ``match`` any number of utterances against it."""
 
     def __init__(self, matching_set: torch.Tensor):
-        from . import _native
-
         if not torch.is_tensor(matching_set) or matching_set.dim() != 2:
             raise ValueError("`matching_set` must be a [M, H] tensor")
         M, H = matching_set.shape
@@ -72,8 +69,7 @@ class KnnIndex:
             raise ValueError("`matching_set` is empty (M = 0): there is nothing to match")
         self.width = int(H)
         self._Hp = _padded_width(self.width)
-        if not matching_set.is_cuda:
-            raise _native.NativeError("audiocodecs_amd.knn runs on MI355X only: move the matching set to a cuda device (there is deliberately no CPU fallback)")
+        _host.need_cuda(matching_set.is_cuda, "knn", "matching set")
         self.device = matching_set.device
         s = matching_set.detach().to(torch.float32)
         if self._Hp != self.width:
@@ -81,25 +77,18 @@ class KnnIndex:
         self.set = s.contiguous()                    # the fp32 rows that are averaged (zero-padded to the compiled width)
         self.rows = int(M)
         self._lib = _native.lib()
-        nbytes = self._lib.ac_knn_packed_bytes(self.rows, self._Hp)
-        if nbytes == 0:
-            raise ValueError(f"ac_knn_packed_bytes refuses M={self.rows}, H={self._Hp}")
-        self.packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.packed = _host.sized_buffer("ac_knn_packed_bytes", self.device, M=self.rows, H=self._Hp)
         with torch.cuda.device(self.device):
-            rc = self._lib.ac_knn_pack(C.c_void_p(self.set.data_ptr()), self.rows, self._Hp, C.c_void_p(self.packed.data_ptr()), nbytes,
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            rc = self._lib.ac_knn_pack(_native._ptr(self.set), self.rows, self._Hp, _native._ptr(self.packed), self.packed.numel(), _native._stream())
         _native.check(rc, None, "ac_knn_pack")
 
     def match(self, feats: torch.Tensor, topk: int = 4, num_splits=None, return_indices: bool = False):
         """feats [..., H] -> [..., H]: per row the mean of its k = min(topk, valid rows) nearest rows.  With `return_indices` also the
         indices [..., topk] (int64, nearest first, -1 behind k) and cosine similarities [..., topk] (fp32, NaN behind k)."""
-        from . import _native
-
         topk, S = _check_topk(topk), _check_splits(num_splits)
         if not torch.is_tensor(feats) or feats.dim() < 1 or feats.shape[-1] != self.width:
             raise ValueError(f"`feats` must be [..., {self.width}] like the matching set (got {tuple(feats.shape) if torch.is_tensor(feats) else type(feats)})")
-        if not feats.is_cuda:
-            raise _native.NativeError("audiocodecs_amd.knn runs on MI355X only: move the features to a cuda device (there is deliberately no CPU fallback)")
+        _host.need_cuda(feats.is_cuda, "knn", "features")
         if feats.device != self.device:
             raise ValueError(f"`feats` is on {feats.device}, the matching set on {self.device}")
         lead = tuple(feats.shape[:-1])
@@ -118,14 +107,11 @@ class KnnIndex:
         out = torch.empty(Q, self._Hp, dtype=torch.float32, device=self.device)
         idx = torch.empty(Q, topk, dtype=torch.int64, device=self.device) if return_indices else None
         sim = torch.empty(Q, topk, dtype=torch.float32, device=self.device) if return_indices else None
-        nws = self._lib.ac_knn_workspace_bytes(Q, self.rows, self._Hp, topk, S)
-        if nws == 0:
-            raise ValueError(f"ac_knn_workspace_bytes refuses Q={Q}, M={self.rows}, H={self._Hp}, topk={topk}, num_splits={S}")
-        ws = torch.empty(nws, dtype=torch.uint8, device=self.device)
+        ws = _host.sized_buffer("ac_knn_workspace_bytes", self.device, Q=Q, M=self.rows, H=self._Hp, topk=topk, num_splits=S)
+        ptr = _native._ptr
         with torch.cuda.device(self.device):
-            rc = self._lib.ac_knn_match(C.c_void_p(q.data_ptr()), Q, C.c_void_p(self.set.data_ptr()), C.c_void_p(self.packed.data_ptr()), self.rows, self._Hp,
-                                        topk, S, C.c_void_p(out.data_ptr()), _native._ptr(idx), _native._ptr(sim), C.c_void_p(ws.data_ptr()), nws,
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            rc = self._lib.ac_knn_match(ptr(q), Q, ptr(self.set), ptr(self.packed), self.rows, self._Hp, topk, S, ptr(out), ptr(idx), ptr(sim), ptr(ws), ws.numel(),
+                                        _native._stream())
         _native.check(rc, None, "ac_knn_match")
         out = out[:, :self.width].reshape(lead + (self.width,))
         if return_indices:

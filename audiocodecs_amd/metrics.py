@@ -27,21 +27,17 @@ restated from pystoi's published algorithm (tests/stoi_ref.py is that statement 
 
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict
-
 import torch
+
+from . import _metric_host as _host
+from . import _native
+from ._metric_host import MAX_HYPS, SAMPLE_RATE
 
 __all__ = ["spectral_distances", "STFTDistance", "MelDistance", "stoi", "STOI", "num_frames", "stoi_num_frames", "SAMPLE_RATE", "N_FFT", "HOP_LENGTH", "N_MELS", "MAX_HYPS"]
 
-SAMPLE_RATE = 16000
 N_FFT = 1024
 HOP_LENGTH = 320
 N_MELS = 80
-MAX_HYPS = 4          # hypotheses per call
-MAX_LEN = 1 << 24
-
-_TABLES: Dict[int, torch.Tensor] = {}
 
 
 def _check_defaults(n_fft=N_FFT, hop_length=HOP_LENGTH, n_mels=N_MELS) -> None:
@@ -57,53 +53,16 @@ def num_frames(length_16k: int) -> int:
     return 1 + int(length_16k) // HOP_LENGTH
 
 
-def _resampled_len(T: int, sample_rate: int) -> int:
-    import math
+def _pair_at_16k(hyp_sig, ref_sig, sample_rate, n):
+    """The refusals that look at the devices, then both signals at 16 kHz, fp32 and contiguous: (hyp [n * B, L16], ref [B, L16])."""
+    from .resample import resample
 
-    g = math.gcd(int(sample_rate), SAMPLE_RATE)
-    return int(math.ceil((SAMPLE_RATE // g) * T / (int(sample_rate) // g)))
-
-
-def _check_args(hyp_sig, ref_sig, sample_rate):
-    """Everything that can be refused without a GPU.  Returns (P or None, B, T)."""
-    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate < 1:
-        raise ValueError(f"`sample_rate` ({sample_rate!r}) must be a positive int")
-    if not torch.is_tensor(hyp_sig) or not torch.is_tensor(ref_sig):
-        raise ValueError("`hyp_sig` and `ref_sig` must be tensors")
-    if ref_sig.dim() != 2:
-        raise ValueError(f"`ref_sig` must be [B, T] (got {tuple(ref_sig.shape)})")
-    if hyp_sig.dim() not in (2, 3) or tuple(hyp_sig.shape[-2:]) != tuple(ref_sig.shape):
-        raise ValueError(f"`hyp_sig` must be [B, T] or [P, B, T] with the shape of `ref_sig` {tuple(ref_sig.shape)} (got {tuple(hyp_sig.shape)})")
-    P = int(hyp_sig.shape[0]) if hyp_sig.dim() == 3 else None
-    if P is not None and not 1 <= P <= MAX_HYPS:
-        raise ValueError(f"`hyp_sig` holds {P} hypotheses: a call takes 1..{MAX_HYPS}")
-    B, T = (int(n) for n in ref_sig.shape)
-    L16 = _resampled_len(T, sample_rate)
-    if L16 > MAX_LEN:
-        raise ValueError(f"signals of {L16} samples at {SAMPLE_RATE} Hz are longer than the {MAX_LEN} a call takes: split them")
-    num_frames(L16)
-    return P, B, T
-
-
-def _tables(device: torch.device) -> torch.Tensor:
-    """The windowed DFT basis and the filterbank as split16 planes, built once per device from the library's fp64 source."""
-    from . import _native
-
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _TABLES:
-        L = _native.lib()
-        n = L.ac_specdist_source_count()
-        src = torch.empty(n, dtype=torch.float64)
-        _native.check(L.ac_specdist_source(C.c_void_p(src.data_ptr()), n), None, "ac_specdist_source")
-        nbytes = L.ac_specdist_tables_bytes()
-        with torch.cuda.device(idx):
-            src_dev = src.to(torch.device("cuda", idx))
-            tables = torch.empty(nbytes, dtype=torch.uint8, device=src_dev.device)
-            rc = L.ac_specdist_tables(C.c_void_p(src_dev.data_ptr()), C.c_void_p(tables.data_ptr()), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _native.check(rc, None, "ac_specdist_tables")
-            torch.cuda.current_stream().synchronize()      # (once per device: src_dev may go, and other streams may use the tables)
-        _TABLES[idx] = tables
-    return _TABLES[idx]
+    _host.need_cuda(hyp_sig.is_cuda and ref_sig.is_cuda, "metrics", "signals")
+    if hyp_sig.device != ref_sig.device:
+        raise ValueError(f"`hyp_sig` is on {hyp_sig.device}, `ref_sig` on {ref_sig.device}")
+    ref = resample(ref_sig.detach().to(torch.float32), sample_rate, SAMPLE_RATE).contiguous()
+    hyp = resample(hyp_sig.detach().to(torch.float32).reshape(n * ref_sig.shape[0], ref_sig.shape[1]), sample_rate, SAMPLE_RATE).contiguous()
+    return hyp, ref
 
 
 @torch.no_grad()
@@ -112,38 +71,24 @@ def spectral_distances(hyp_sig: torch.Tensor, ref_sig: torch.Tensor, sample_rate
     (or [P, B]) fp32 on the signals' device.  With `return_frames` also the per-frame distances the scores are the means of:
     (stft, mel, stft_frames, mel_frames), the last two [B, F] (or [P, B, F]).  The rows of a [P, B, T] call are bit for bit those of P
     separate calls; a clip that holds an inf or a NaN gets NaN scores and disturbs no other clip."""
-    from . import _native
-    from .resample import resample
-
-    P, B, T = _check_args(hyp_sig, ref_sig, sample_rate)
+    P, B, _, L16 = _host.check_pair(hyp_sig, ref_sig, sample_rate)
     dev = ref_sig.device
     lead = () if P is None else (P,)
-    F = num_frames(_resampled_len(T, sample_rate))
+    F = num_frames(L16)
     if B == 0:            # an empty shard: the empty result (the library is not called)
         out = tuple(torch.empty(lead + (0,), dtype=torch.float32, device=dev) for _ in range(2))
         return out + tuple(torch.empty(lead + (0, F), dtype=torch.float32, device=dev) for _ in range(2)) if return_frames else out
-    if not (hyp_sig.is_cuda and ref_sig.is_cuda):
-        raise _native.NativeError("audiocodecs_amd.metrics runs on MI355X only: move the signals to a cuda device (there is deliberately no CPU fallback)")
-    if hyp_sig.device != dev:
-        raise ValueError(f"`hyp_sig` is on {hyp_sig.device}, `ref_sig` on {dev}")
     n = 1 if P is None else P
-    ref = resample(ref_sig.detach().to(torch.float32), sample_rate, SAMPLE_RATE).contiguous()
-    hyp = resample(hyp_sig.detach().to(torch.float32).reshape(n * B, T), sample_rate, SAMPLE_RATE).contiguous()
-    L16 = int(ref.shape[1])
-    L = _native.lib()
-    tables = _tables(dev)
+    hyp, ref = _pair_at_16k(hyp_sig, ref_sig, sample_rate, n)
+    tables = _host.tables("specdist", dev)
     stft = torch.empty(n, B, dtype=torch.float32, device=dev)
     mel = torch.empty(n, B, dtype=torch.float32, device=dev)
     sfr = torch.empty(n, B, F, dtype=torch.float32, device=dev) if return_frames else None
     mfr = torch.empty(n, B, F, dtype=torch.float32, device=dev) if return_frames else None
-    nws = L.ac_specdist_workspace_bytes(n, B, L16)
-    if nws == 0:
-        raise ValueError(f"ac_specdist_workspace_bytes refuses P={n}, B={B}, L={L16}")
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    ws = _host.sized_buffer("ac_specdist_workspace_bytes", dev, P=n, B=B, L=L16)
+    ptr = _native._ptr
     with torch.cuda.device(dev):
-        rc = L.ac_specdist(C.c_void_p(hyp.data_ptr()), C.c_void_p(ref.data_ptr()), n, B, L16, C.c_void_p(tables.data_ptr()), C.c_void_p(stft.data_ptr()),
-                           C.c_void_p(mel.data_ptr()), _native._ptr(sfr), _native._ptr(mfr), C.c_void_p(ws.data_ptr()), nws,
-                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = _native.lib().ac_specdist(ptr(hyp), ptr(ref), n, B, L16, ptr(tables), ptr(stft), ptr(mel), ptr(sfr), ptr(mfr), ptr(ws), ws.numel(), _native._stream())
     _native.check(rc, None, "ac_specdist")
     shape = lead + (B,)
     if return_frames:
@@ -168,10 +113,14 @@ class _DistanceStats:
         """`lens` is accepted and ignored, as the reference ignores it."""
         if not torch.is_tensor(hyp_sig) or not torch.is_tensor(ref_sig) or hyp_sig.shape != ref_sig.shape or hyp_sig.dim() != 2:
             raise ValueError("`hyp_sig` and `ref_sig` must be [B, T] tensors of the same shape")
+        self._record(ids, hyp_sig.shape[0], lambda: self._scores(hyp_sig, ref_sig))
+
+    def _record(self, ids, B, scores) -> None:
+        """One id per clip, then `scores()` [B] behind them."""
         ids = list(ids)
-        if len(ids) != hyp_sig.shape[0]:
-            raise ValueError(f"{len(ids)} ids for {hyp_sig.shape[0]} clips")
-        scores = self._scores(hyp_sig, ref_sig)
+        if len(ids) != B:
+            raise ValueError(f"{len(ids)} ids for {B} clips")
+        scores = scores()
         self.ids += ids
         self.scores += scores.cpu().tolist()
 
@@ -223,8 +172,6 @@ class MelDistance(_DistanceStats):
 STOI_MIN_LEN_10K = 256          # one frame at 10 kHz
 STOI_SEGMENT = 30               # frames per segment
 
-_STOI_TABLES: Dict[int, torch.Tensor] = {}
-
 
 def stoi_num_frames(length_16k: int) -> int:
     """Frames of 256 at hop 128 of a signal of `length_16k` samples at 16 kHz once it stands at 10 kHz (before the silent ones go):
@@ -235,49 +182,6 @@ def stoi_num_frames(length_16k: int) -> int:
     return (L10 - STOI_MIN_LEN_10K) // 128 + 1
 
 
-def _check_stoi_args(hyp_sig, ref_sig, sample_rate, extended):
-    """Everything that can be refused without a GPU.  Returns (P or None, B, T, F0)."""
-    if extended is not False:
-        raise ValueError(f"only the reference's default is compiled: extended=False (got extended={extended!r})")
-    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate < 1:
-        raise ValueError(f"`sample_rate` ({sample_rate!r}) must be a positive int")
-    if not torch.is_tensor(hyp_sig) or not torch.is_tensor(ref_sig):
-        raise ValueError("`hyp_sig` and `ref_sig` must be tensors")
-    if ref_sig.dim() != 2:
-        raise ValueError(f"`ref_sig` must be [B, T] (got {tuple(ref_sig.shape)})")
-    if hyp_sig.dim() not in (2, 3) or tuple(hyp_sig.shape[-2:]) != tuple(ref_sig.shape):
-        raise ValueError(f"`hyp_sig` must be [B, T] or [P, B, T] with the shape of `ref_sig` {tuple(ref_sig.shape)} (got {tuple(hyp_sig.shape)})")
-    P = int(hyp_sig.shape[0]) if hyp_sig.dim() == 3 else None
-    if P is not None and not 1 <= P <= MAX_HYPS:
-        raise ValueError(f"`hyp_sig` holds {P} hypotheses: a call takes 1..{MAX_HYPS}")
-    B, T = (int(n) for n in ref_sig.shape)
-    L16 = _resampled_len(T, sample_rate)
-    if L16 > MAX_LEN:
-        raise ValueError(f"signals of {L16} samples at {SAMPLE_RATE} Hz are longer than the {MAX_LEN} a call takes: split them")
-    return P, B, T, stoi_num_frames(L16)
-
-
-def _stoi_tables(device: torch.device) -> torch.Tensor:
-    """The window, the 16 -> 10 kHz FIR bank and the windowed DFT basis (split16 planes), built once per device from the library's fp64 source."""
-    from . import _native
-
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _STOI_TABLES:
-        L = _native.lib()
-        n = L.ac_stoi_source_count()
-        src = torch.empty(n, dtype=torch.float64)
-        _native.check(L.ac_stoi_source(C.c_void_p(src.data_ptr()), n), None, "ac_stoi_source")
-        nbytes = L.ac_stoi_tables_bytes()
-        with torch.cuda.device(idx):
-            src_dev = src.to(torch.device("cuda", idx))
-            tables = torch.empty(nbytes, dtype=torch.uint8, device=src_dev.device)
-            rc = L.ac_stoi_tables(C.c_void_p(src_dev.data_ptr()), C.c_void_p(tables.data_ptr()), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _native.check(rc, None, "ac_stoi_tables")
-            torch.cuda.current_stream().synchronize()      # (once per device: src_dev may go, and other streams may use the tables)
-        _STOI_TABLES[idx] = tables
-    return _STOI_TABLES[idx]
-
-
 @torch.no_grad()
 def stoi(hyp_sig: torch.Tensor, ref_sig: torch.Tensor, sample_rate: int, extended: bool = False, return_details: bool = False):
     """hyp_sig [B, T] (or [P, B, T]: P hypotheses of the same clips), ref_sig [B, T] (the clean signal), both at `sample_rate` -> the STOI
@@ -285,10 +189,10 @@ def stoi(hyp_sig: torch.Tensor, ref_sig: torch.Tensor, sample_rate: int, extende
     the frames the silent-frame rule keeps; num_segments [B] int32; segments [B, max(F0 - 30, 0)] (or [P, B, ...]) fp32, per segment the
     sum of the 15 band correlations / 15, NaN past num_segments.  Fewer than 30 frames left give 1e-5, as pystoi does.  The rows of a
     [P, B, T] call are bit for bit those of P separate calls; a clip that holds an inf or a NaN gets a NaN score and disturbs no other."""
-    from . import _native
-    from .resample import resample
-
-    P, B, T, F0 = _check_stoi_args(hyp_sig, ref_sig, sample_rate, extended)
+    if extended is not False:
+        raise ValueError(f"only the reference's default is compiled: extended=False (got extended={extended!r})")
+    P, B, _, L16 = _host.check_pair(hyp_sig, ref_sig, sample_rate)
+    F0 = stoi_num_frames(L16)
     dev = ref_sig.device
     lead = () if P is None else (P,)
     NS0 = max(F0 - STOI_SEGMENT, 0)
@@ -298,28 +202,17 @@ def stoi(hyp_sig: torch.Tensor, ref_sig: torch.Tensor, sample_rate: int, extende
             return score
         return (score, torch.empty(0, F0, dtype=torch.bool, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
                 torch.empty(lead + (0, NS0), dtype=torch.float32, device=dev))
-    if not (hyp_sig.is_cuda and ref_sig.is_cuda):
-        raise _native.NativeError("audiocodecs_amd.metrics runs on MI355X only: move the signals to a cuda device (there is deliberately no CPU fallback)")
-    if hyp_sig.device != dev:
-        raise ValueError(f"`hyp_sig` is on {hyp_sig.device}, `ref_sig` on {dev}")
     n = 1 if P is None else P
-    ref = resample(ref_sig.detach().to(torch.float32), sample_rate, SAMPLE_RATE).contiguous()
-    hyp = resample(hyp_sig.detach().to(torch.float32).reshape(n * B, T), sample_rate, SAMPLE_RATE).contiguous()
-    L16 = int(ref.shape[1])
-    L = _native.lib()
-    tables = _stoi_tables(dev)
+    hyp, ref = _pair_at_16k(hyp_sig, ref_sig, sample_rate, n)
+    tables = _host.tables("stoi", dev)
     score = torch.empty(n, B, dtype=torch.float32, device=dev)
     kept = torch.empty(B, F0, dtype=torch.bool, device=dev) if return_details else None
     nseg = torch.empty(B, dtype=torch.int32, device=dev) if return_details else None
     segs = torch.empty(n, B, NS0, dtype=torch.float32, device=dev) if return_details else None
-    nws = L.ac_stoi_workspace_bytes(n, B, L16)
-    if nws == 0:
-        raise ValueError(f"ac_stoi_workspace_bytes refuses P={n}, B={B}, L16={L16}")
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    ws = _host.sized_buffer("ac_stoi_workspace_bytes", dev, P=n, B=B, L16=L16)
+    ptr = _native._ptr
     with torch.cuda.device(dev):
-        rc = L.ac_stoi(C.c_void_p(hyp.data_ptr()), C.c_void_p(ref.data_ptr()), n, B, L16, C.c_void_p(tables.data_ptr()), C.c_void_p(score.data_ptr()),
-                       _native._ptr(kept), _native._ptr(nseg), _native._ptr(segs), C.c_void_p(ws.data_ptr()), nws,
-                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = _native.lib().ac_stoi(ptr(hyp), ptr(ref), n, B, L16, ptr(tables), ptr(score), ptr(kept), ptr(nseg), ptr(segs), ptr(ws), ws.numel(), _native._stream())
     _native.check(rc, None, "ac_stoi")
     shape = lead + (B,)
     if return_details:

@@ -19,9 +19,10 @@ normalised entropy.  There is no CPU fallback.
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
+
+from . import _metric_host as _host
+from . import _native
 
 __all__ = ["token_histogram", "codebook_stats", "tokstats_form", "TokenStatsState", "CodebookUtil", "MAX_CODEBOOKS", "MIN_VOCAB", "MAX_VOCAB"]
 
@@ -42,8 +43,6 @@ def _check_shape(num_codebooks, vocab_size) -> None:
 
 def tokstats_form(num_codebooks: int, vocab_size: int):
     """("tiled", G) or ("direct", 0): the form a histogram of this shape takes (a pure function of the two; no GPU)."""
-    from . import _native
-
     _check_shape(num_codebooks, vocab_size)
     G = _native.lib().ac_tokstats_form(num_codebooks, vocab_size)
     _native.check(G, None, "ac_tokstats_form")
@@ -55,12 +54,9 @@ class TokenStatsState:
     ``bad`` (ids outside [0, C) among them); the three attributes are views of it."""
 
     def __init__(self, num_codebooks: int, vocab_size: int, device):
-        from . import _native
-
         _check_shape(num_codebooks, vocab_size)
         device = torch.device(device)
-        if device.type != "cuda":
-            raise _native.NativeError("audiocodecs_amd.tokstats runs on MI355X only: the state lives on a cuda device (there is deliberately no CPU fallback)")
+        _host.need_cuda(device.type == "cuda", "tokstats", "state", "the {} lives on")
         self.num_codebooks, self.vocab_size = num_codebooks, vocab_size
         self.buf = torch.zeros(num_codebooks * vocab_size + 2, dtype=torch.int64, device=device)
 
@@ -93,14 +89,11 @@ def token_histogram(toks: torch.Tensor, vocab_size: int, lens=None, out=None) ->
     """toks [B, N, K] (any integer dtype) -> counts [K, vocab_size] int64 on the tokens' device.  `lens` [B], relative: clip b contributes
     its first clamp(round(lens[b] * N), 0, N) frames.  `out` accumulates: a `TokenStatsState` (its `total` and `bad` are kept too) or an
     int64 [K, vocab_size] tensor of counts; the counts are returned either way.  Ids outside [0, vocab_size) are not counted."""
-    from . import _native
-
     if not torch.is_tensor(toks) or toks.dim() != 3 or toks.is_floating_point() or toks.is_complex() or toks.dtype == torch.bool:
         raise ValueError("`toks` must be a [B, N, K] tensor of an integer dtype")
     B, N, K = (int(n) for n in toks.shape)
     _check_shape(K, vocab_size)
-    if not toks.is_cuda:
-        raise _native.NativeError("audiocodecs_amd.tokstats runs on MI355X only: move the tokens to a cuda device (there is deliberately no CPU fallback)")
+    _host.need_cuda(toks.is_cuda, "tokstats", "tokens")
     dev = toks.device
     state = out if isinstance(out, TokenStatsState) else TokenStatsState(K, vocab_size, dev)
     if (state.num_codebooks, state.vocab_size) != (K, vocab_size) or state.buf.device != dev:
@@ -113,7 +106,7 @@ def token_histogram(toks: torch.Tensor, vocab_size: int, lens=None, out=None) ->
     toks = toks.detach().to(torch.int64).contiguous()
     L = _native.lib()
     with torch.cuda.device(dev):
-        rc = L.ac_tokstats_accumulate(C.c_void_p(toks.data_ptr()), B, N, K, vocab_size, _native._ptr(nvalid), C.c_void_p(state.buf.data_ptr()),
+        rc = L.ac_tokstats_accumulate(_native._ptr(toks), B, N, K, vocab_size, _native._ptr(nvalid), _native._ptr(state.buf),
                                       state.buf.numel() * 8, _native._stream())
     _native.check(rc, None, "ac_tokstats_accumulate")
     if out is not None and state is not out:
@@ -126,8 +119,6 @@ def token_histogram(toks: torch.Tensor, vocab_size: int, lens=None, out=None) ->
 def codebook_stats(counts_or_state) -> torch.Tensor:
     """A `TokenStatsState`, or int64 counts [K, C] whose rows each sum to the number of frames -> [K, 4] fp64 on the same device:
     per codebook (ids in use, entropy in bits, utilisation, normalised entropy); the last two are 0 unless two ids are in use."""
-    from . import _native
-
     state = counts_or_state
     if not isinstance(state, TokenStatsState):
         counts = counts_or_state
@@ -140,7 +131,7 @@ def codebook_stats(counts_or_state) -> torch.Tensor:
     out = torch.empty(K, 4, dtype=torch.float64, device=state.buf.device)
     L = _native.lib()
     with torch.cuda.device(state.buf.device):
-        rc = L.ac_tokstats_summary(C.c_void_p(state.buf.data_ptr()), K, Cv, C.c_void_p(out.data_ptr()), _native._stream())
+        rc = L.ac_tokstats_summary(_native._ptr(state.buf), K, Cv, _native._ptr(out), _native._stream())
     _native.check(rc, None, "ac_tokstats_summary")
     return out
 
@@ -166,12 +157,9 @@ class CodebookUtil:
     @torch.no_grad()
     def append(self, hyp_toks, lens=None) -> None:
         """hyp_toks [B, N, K]; `lens` [B] relative or None.  No host copy, no synchronisation."""
-        from . import _native
-
         if not torch.is_tensor(hyp_toks) or hyp_toks.dim() != 3 or hyp_toks.shape[-1] != self.num_codebooks:
             raise ValueError(f"`hyp_toks` must be [B, N, {self.num_codebooks}]")
-        if not hyp_toks.is_cuda:
-            raise _native.NativeError("audiocodecs_amd.tokstats runs on MI355X only: move the tokens to a cuda device (there is deliberately no CPU fallback)")
+        _host.need_cuda(hyp_toks.is_cuda, "tokstats", "tokens")
         if self.state is None:
             self.state = TokenStatsState(self.num_codebooks, self.vocab_size, hyp_toks.device)
         token_histogram(hyp_toks, self.vocab_size, lens=lens, out=self.state)

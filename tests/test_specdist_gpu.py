@@ -224,7 +224,7 @@ def test_abi_refusals_launch_nothing():
     lib = _native.lib()
     P, B, L = 1, 2, 5121
     hyp, ref = (dev(a) for a in R.make_pair("noise", 12, B, L))
-    tables = metrics._tables(hyp.device)
+    tables = metrics._host.tables("specdist", hyp.device)
     nws = lib.ac_specdist_workspace_bytes(P, B, L)
     ws = torch.zeros(nws + 16, dtype=torch.uint8, device="cuda")
     so, mo = torch.full((B,), 7.0, device="cuda"), torch.full((B,), 7.0, device="cuda")

@@ -249,7 +249,7 @@ def test_abi_refusals_launch_nothing():
     hyp, ref = case_data("gaps", L, B, 1)
     hyp, ref = dev(hyp[0]), dev(ref)
     F0 = R.num_frames(L)
-    tables = metrics._stoi_tables(hyp.device)
+    tables = metrics._host.tables("stoi", hyp.device)
     nws = lib.ac_stoi_workspace_bytes(P, B, L)
     ws = torch.zeros(nws + 16, dtype=torch.uint8, device="cuda")
     score = torch.full((B,), 7.0, device="cuda")

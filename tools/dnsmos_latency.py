@@ -15,12 +15,8 @@ Every call is timed on the host from the call to the scores being on the host.  
 absolute difference of the fused scores from the other two and the shader clock sampled while calls are queued (None where the platform
 reports none).  Reported, not gated: there is no threshold."""
 import argparse
-import json
 import os
-import re
-import subprocess
 import sys
-import time
 
 import numpy as np
 import torch
@@ -32,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from audiocodecs_amd import dnsmos, dnsmos_segments  # noqa: E402
 from audiocodecs_amd.dnsmos import load_weights  # noqa: E402
 from audiocodecs_amd.resample import resample  # noqa: E402
+from latency_common import alternate, emit, median_p99, shader_mhz  # noqa: E402
 
 RATE = 24000
 SECONDS = 10
@@ -72,19 +69,6 @@ def host_regime(sig, R):
     return np.array([R.score_clip(c)[0] for c in x])
 
 
-def shader_mhz():
-    try:
-        return round(torch.cuda.clock_rate(), 0)
-    except Exception:
-        pass
-    try:
-        txt = subprocess.run(["rocm-smi", "--showclocks", "-d", str(torch.cuda.current_device())], capture_output=True, text=True, timeout=20).stdout
-        m = re.search(r"sclk clock level:.*?\((\d+)Mhz\)", txt)
-        return float(m.group(1)) if m else None
-    except Exception:
-        return None
-
-
 def main():
     import dnsmos_ref as R
 
@@ -104,30 +88,14 @@ def main():
     for _ in range(a.warmup):
         dnsmos(sig, RATE, weights).cpu()
         chain(sig).cpu()
-    lat = {"fused": [], "torch": [], "host": []}
-    fused = tch = host = None
-    for i in range(max(a.calls, a.torch_calls, a.host_calls)):
-        if i < a.calls:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fused = dnsmos(sig, RATE, weights).cpu()
-            lat["fused"].append((time.perf_counter() - t0) * 1e3)
-        if i < a.torch_calls:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            tch = chain(sig).cpu()
-            lat["torch"].append((time.perf_counter() - t0) * 1e3)
-        if i < a.host_calls:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            host = host_regime(sig, R)
-            lat["host"].append((time.perf_counter() - t0) * 1e3)
+    forms = {"fused": lambda: dnsmos(sig, RATE, weights).cpu(), "torch": lambda: chain(sig).cpu(), "host": lambda: host_regime(sig, R)}
+    lat, last = alternate(forms, {"fused": a.calls, "torch": a.torch_calls, "host": a.host_calls}, sync=False)      # (every form ends on the host)
+    fused, tch, host = (last.get(name) for name in forms)
     row = {"clips": B, "seconds": SECONDS, "rate": RATE, "windows": B * len(dnsmos_segments(SECONDS * 16000)), "calls": a.calls, "torch_calls": a.torch_calls,
            "host_calls": a.host_calls, "warmup": a.warmup}
     for name, v in lat.items():
         if v:
-            row[f"{name}_median_ms"] = round(float(np.median(v)), 3)
-            row[f"{name}_p99_ms"] = round(float(np.percentile(v, 99)), 3)
+            row.update(median_p99(v, prefix=f"{name}_"))
     for _ in range(5):
         dnsmos(sig, RATE, weights)
     row["shader_mhz"] = shader_mhz()
@@ -136,11 +104,7 @@ def main():
         row["largest_difference_from_torch"] = float((fused.double() - tch.double()).abs().max())
     if host is not None:
         row["largest_difference_from_host"] = float(np.abs(fused.numpy().astype(np.float64) - host).max())
-    print(json.dumps(row), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write(json.dumps(row) + "\n")
+    emit(row, a.out)
 
 
 if __name__ == "__main__":

@@ -14,14 +14,9 @@ split count the library chose, the agreement of the two results (rows whose neig
 matches are queued (None where the platform reports none).  The timed calls per form are `--calls` or as many as keep the fastest form
 busy for `--window` seconds, whichever is more.  Reported, not gated: there is no threshold."""
 import argparse
-import json
 import os
-import re
-import subprocess
 import sys
-import time
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,6 +24,7 @@ sys.path.insert(0, ROOT)
 
 from audiocodecs_amd import KnnIndex, knn_match  # noqa: E402
 from audiocodecs_amd.knn import auto_splits  # noqa: E402
+from latency_common import alternate_for, emit, median_p99, shader_mhz  # noqa: E402
 
 SHAPES = ((400, 2400), (400, 24000), (25600, 24000))
 H, TOPK = 512, 4
@@ -42,19 +38,6 @@ def torch_helper(q, t, topk):
     return t[idx].mean(dim=-2), idx
 
 
-def shader_mhz():
-    try:
-        return round(torch.cuda.clock_rate(), 0)
-    except Exception:
-        pass
-    try:
-        txt = subprocess.run(["rocm-smi", "--showclocks", "-d", str(torch.cuda.current_device())], capture_output=True, text=True, timeout=20).stdout
-        m = re.search(r"sclk clock level:.*?\((\d+)Mhz\)", txt)
-        return float(m.group(1)) if m else None
-    except Exception:
-        return None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=100, help="least number of timed calls per form and shape")
@@ -63,7 +46,6 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
-    lines = []
     for Q, M in SHAPES:
         g = torch.Generator().manual_seed(Q + M)
         centres = torch.randn(200, H, generator=g)                # feature-like rows: clusters of directions with noise and a spread of norms
@@ -76,24 +58,11 @@ def main():
             "per_call": lambda: knn_match(q, t, topk=TOPK),
             "torch": lambda: torch_helper(q, t, TOPK)[0],
         }
-        calls = a.calls
-        lat = {k: [] for k in forms}
-        i, warm = 0, []
-        while i < a.warmup + calls:
-            for name, fn in forms.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                out = fn()
-                torch.cuda.synchronize()
-                (lat[name] if i >= a.warmup else warm).append((time.perf_counter() - t0) * 1e3)
-                assert out.shape == (Q, H)
-            i += 1
-            if i == a.warmup:
-                calls = min(a.max_calls, max(a.calls, int(a.window * 1e3 / min(warm)) + 1))
+        lat, last, calls = alternate_for(forms, a.calls, a.window, a.max_calls, a.warmup)
+        assert all(out.shape == (Q, H) for out in last.values())
         row = {"Q": Q, "M": M, "H": H, "topk": TOPK, "num_splits": auto_splits(Q, M, H), "calls": calls, "warmup": a.warmup}
         for name, v in lat.items():
-            row[f"{name}_median_ms"] = round(float(np.median(v)), 3)
-            row[f"{name}_p99_ms"] = round(float(np.percentile(v, 99)), 3)
+            row.update(median_p99(v, prefix=f"{name}_"))
         for _ in range(20):
             index.match(q, topk=TOPK)
         row["shader_mhz"] = shader_mhz()
@@ -101,11 +70,7 @@ def main():
         _, idx, _ = index.match(q, topk=TOPK, return_indices=True)
         tidx = torch_helper(q, t, TOPK)[1]
         row["rows_with_the_same_neighbour_set"] = int((idx.sort(dim=-1).values == tidx.sort(dim=-1).values).all(dim=-1).sum())
-        print(json.dumps(row), flush=True)
-        lines.append(json.dumps(row))
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        emit(row, a.out)
 
 
 if __name__ == "__main__":

@@ -14,14 +14,9 @@ Every call is timed on the host from the call to a stream synchronisation.  One 
 the largest relative difference of the two results and the shader clock sampled while calls are queued (None where the platform
 reports none).  Reported, not gated: there is no threshold."""
 import argparse
-import json
 import os
-import re
-import subprocess
 import sys
-import time
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,6 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from audiocodecs_amd import spectral_distances  # noqa: E402
 from audiocodecs_amd.resample import resample  # noqa: E402
+from latency_common import alternate_for, emit, median_p99, shader_mhz  # noqa: E402
 
 SHAPES = ((64, 10, 1), (64, 10, 3), (1, 10, 1))
 RATE = 24000
@@ -51,19 +47,6 @@ def torch_restatement(hyp, ref, fb, win):
     return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])
 
 
-def shader_mhz():
-    try:
-        return round(torch.cuda.clock_rate(), 0)
-    except Exception:
-        pass
-    try:
-        txt = subprocess.run(["rocm-smi", "--showclocks", "-d", str(torch.cuda.current_device())], capture_output=True, text=True, timeout=20).stdout
-        m = re.search(r"sclk clock level:.*?\((\d+)Mhz\)", txt)
-        return float(m.group(1)) if m else None
-    except Exception:
-        return None
-
-
 def main():
     import specdist_ref as R
 
@@ -76,7 +59,6 @@ def main():
     a = ap.parse_args()
     fb = torch.from_numpy(R.filterbank()).float().cuda()
     win = torch.hann_window(1024, device="cuda")
-    lines = []
     for B, secs, P in SHAPES:
         g = torch.Generator().manual_seed(B + P)
         T = secs * RATE
@@ -86,24 +68,11 @@ def main():
             "fused": lambda: spectral_distances(hyp, ref, RATE),
             "torch": lambda: torch_restatement(hyp, ref, fb, win),
         }
-        calls = a.calls
-        lat = {k: [] for k in forms}
-        i, warm = 0, []
-        while i < a.warmup + calls:
-            for name, fn in forms.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                out = fn()
-                torch.cuda.synchronize()
-                (lat[name] if i >= a.warmup else warm).append((time.perf_counter() - t0) * 1e3)
-                assert out[0].shape == (P, B)
-            i += 1
-            if i == a.warmup:
-                calls = min(a.max_calls, max(a.calls, int(a.window * 1e3 / min(warm)) + 1))
+        lat, last, calls = alternate_for(forms, a.calls, a.window, a.max_calls, a.warmup)
+        assert all(out[0].shape == (P, B) for out in last.values())
         row = {"clips": B, "seconds": secs, "rate": RATE, "P": P, "frames": 1 + (secs * 16000) // 320, "calls": calls, "warmup": a.warmup}
         for name, v in lat.items():
-            row[f"{name}_median_ms"] = round(float(np.median(v)), 3)
-            row[f"{name}_p99_ms"] = round(float(np.percentile(v, 99)), 3)
+            row.update(median_p99(v, prefix=f"{name}_"))
         for _ in range(20):
             spectral_distances(hyp, ref, RATE)
         row["shader_mhz"] = shader_mhz()
@@ -111,12 +80,7 @@ def main():
         fs, fm = spectral_distances(hyp, ref, RATE)
         ts, tm = torch_restatement(hyp, ref, fb, win)
         row["largest_relative_difference"] = float(max(((fs - ts).abs() / ts.abs()).max(), ((fm - tm).abs() / tm.abs()).max()))
-        print(json.dumps(row), flush=True)
-        lines.append(json.dumps(row))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        emit(row, a.out)
 
 
 if __name__ == "__main__":

@@ -13,12 +13,8 @@ Every call is timed on the host from the call to the scores being on the host.  
 the largest absolute difference of the two results and the shader clock sampled while calls are queued (None where the platform
 reports none).  Reported, not gated: there is no threshold."""
 import argparse
-import json
 import os
-import re
-import subprocess
 import sys
-import time
 
 import numpy as np
 import torch
@@ -29,6 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from audiocodecs_amd import stoi  # noqa: E402
 from audiocodecs_amd.resample import resample  # noqa: E402
+from latency_common import alternate, emit, median_p99, shader_mhz  # noqa: E402
 
 SHAPES = ((64, 10, 1), (64, 10, 3), (1, 10, 1))
 RATE = 24000
@@ -43,19 +40,6 @@ def host_regime(hyp, ref, R):
     return np.array(out)
 
 
-def shader_mhz():
-    try:
-        return round(torch.cuda.clock_rate(), 0)
-    except Exception:
-        pass
-    try:
-        txt = subprocess.run(["rocm-smi", "--showclocks", "-d", str(torch.cuda.current_device())], capture_output=True, text=True, timeout=20).stdout
-        m = re.search(r"sclk clock level:.*?\((\d+)Mhz\)", txt)
-        return float(m.group(1)) if m else None
-    except Exception:
-        return None
-
-
 def main():
     import stoi_ref as R
 
@@ -65,7 +49,6 @@ def main():
     ap.add_argument("--warmup", type=int, default=3, help="untimed calls of the fused form (one of the host form)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
-    lines = []
     for B, secs, P in SHAPES:
         T = secs * RATE
         ref = torch.from_numpy(np.stack([R.make_clip("gaps", 1000 * B + b, T) for b in range(B)])).cuda()
@@ -74,33 +57,17 @@ def main():
         for _ in range(a.warmup):
             stoi(hyp, ref, RATE).cpu()
         host_regime(hyp, ref, R)
-        lat = {"fused": [], "host": []}
-        for i in range(max(a.calls, a.host_calls)):
-            if i < a.calls:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                fused = stoi(hyp, ref, RATE).cpu()
-                lat["fused"].append((time.perf_counter() - t0) * 1e3)
-            if i < a.host_calls:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                host = host_regime(hyp, ref, R)
-                lat["host"].append((time.perf_counter() - t0) * 1e3)
+        forms = {"fused": lambda: stoi(hyp, ref, RATE).cpu(), "host": lambda: host_regime(hyp, ref, R)}
+        lat, last = alternate(forms, {"fused": a.calls, "host": a.host_calls}, sync=False)      # (both forms end on the host)
         row = {"clips": B, "seconds": secs, "rate": RATE, "P": P, "frames": R.num_frames(secs * 16000), "calls": a.calls, "host_calls": a.host_calls, "warmup": a.warmup}
         for name, v in lat.items():
-            row[f"{name}_median_ms"] = round(float(np.median(v)), 3)
-            row[f"{name}_p99_ms"] = round(float(np.percentile(v, 99)), 3)
+            row.update(median_p99(v, prefix=f"{name}_"))
         for _ in range(20):
             stoi(hyp, ref, RATE)
         row["shader_mhz"] = shader_mhz()
         torch.cuda.synchronize()
-        row["largest_absolute_difference"] = float(np.abs(fused.numpy().astype(np.float64) - host).max())
-        print(json.dumps(row), flush=True)
-        lines.append(json.dumps(row))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        row["largest_absolute_difference"] = float(np.abs(last["fused"].numpy().astype(np.float64) - last["host"]).max())
+        emit(row, a.out)
 
 
 if __name__ == "__main__":

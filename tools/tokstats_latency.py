@@ -15,10 +15,8 @@ The report part runs the full-size EnCodec with seeded random weights on 64 clip
 `resynthesis_report` against `resynthesis_distances` + `resynthesis_stoi` + `resynthesis_dnsmos`, host clock up to a synchronise.
 Reported, not gated: there is no threshold."""
 import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -28,6 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from audiocodecs_amd import CodebookUtil  # noqa: E402
+from latency_common import emit, host_timed, median_p99  # noqa: E402
 
 SHAPES = [("encodec", 64, 750, 8, 1024), ("mimi", 128, 125, 8, 2048)]
 
@@ -43,15 +42,7 @@ def reference_append(counts, toks):
 
 
 def stats(ms):
-    return {"median_ms": round(float(np.median(ms)), 4), "p99_ms": round(float(np.percentile(ms, 99)), 4), "repeats": len(ms)}
-
-
-def host_timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
+    return {**median_p99(ms, digits=4), "repeats": len(ms)}
 
 
 def event_timed(fn):
@@ -127,14 +118,8 @@ def main():
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     jobs = [lambda shape=shape: measure_append(*shape, a) for shape in SHAPES] + ([] if a.no_report else [lambda: measure_report(a)])
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     for job in jobs:
-        row = job()
-        print(json.dumps(row), flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(json.dumps(row) + "\n")
+        emit(job(), a.out)
 
 
 if __name__ == "__main__":
