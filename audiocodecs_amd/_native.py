@@ -238,6 +238,8 @@ EXPORTS = {
     "ac_tokstats_form": (_i, [_i, _i]),
     "ac_tokstats_accumulate": (_i, [_vp, _ll, _ll, _i, _i, _vp, _vp, _sz, _vp]),
     "ac_tokstats_summary": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ac_sample_form": (_i, [_i]),
+    "ac_sample_tokens": (_i, [_vp, _ll, _vp, _ll, _i, C.c_float, _i, C.c_float, C.c_uint64, C.c_uint64, _vp, C.c_float, _vp, _vp, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

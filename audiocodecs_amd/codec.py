@@ -262,7 +262,15 @@ class Codec(torch.nn.Module, ABC):
 
     # ---- token-resampling utilities: a step-for-step restatement of /root/reference/audiocodecs/codec.py:121-180 (same RNG call order;
     #      no caller in the reference tree) --------
-    def resample(self, toks, p=0.2, temp=1.0, top_k=None, top_p=None):
+    #      With a `seed` the same resampling runs as one launch of the library (sampling.py): the draws come from
+    #      the repository's counter-based PRNG at `(seed, offset)`, not from torch's generator.
+    def resample(self, toks, p=0.2, temp=1.0, top_k=None, top_p=None, seed=None, offset=0):
+        if seed is not None:
+            if p <= 0.0:
+                return toks
+            from .sampling import resample_tokens
+
+            return resample_tokens(toks, self.logits(), p, temp=temp, top_k=top_k, top_p=top_p, seed=seed, offset=offset)
         if p <= 0.0:
             return toks
         out = toks.clone()

@@ -14,6 +14,8 @@
 //                   includes nothing of the above
 //   tokstats.hip    the token histogram and the codebook utilisation summary (tokstats.h) and the handle-free ac_tokstats_* entry points;
 //                   includes nothing of the above
+//   sampling.hip    fused token sampling and masked token resampling (sampling.h) and the handle-free ac_sample_* entry points; includes
+//                   nothing of the above and takes the pointer alignment rule and the launch status from metric_host.h
 //                   -- these five (knn .. tokstats) share their host side through metric_host.h: the pointer alignment rule, the status behind the
 //                   launches, the octant-reduced cosine, the triangular filterbank and the workspace cursor; the fp64 ->
 //                   fp16-pair split of their table kernels is s16_split64 (split16.h)

@@ -675,6 +675,36 @@ int ac_tokstats_accumulate(const int64_t* toks_dev, long long B, long long N, in
                            size_t state_bytes, void* stream);
 int ac_tokstats_summary(const void* state_dev, int K, int C, double* out_dev, void* stream);
 
+/* Fused token sampling and masked token resampling (handle-free): the reference's chain of softmax, top-k or top-p,
+ * multinomial and gather (codec.py:121-180, downstream/models/llama3.py:944-996) for R rows of C logits in ONE launch, each row's draw
+ * addressed by a counter of the repository's PRNG (audiocodecs_amd/prng.py) so that a result can be checked token by token.
+ *   ac_sample_form(C)   1: one wave per row (C <= 1024); 2: one workgroup of ceil(C / 1024) waves per row.  A pure function of C;
+ *                       AC_EINVAL outside 2 <= C <= 16384.
+ *   ac_sample_tokens    row r reads C fp32 logits at logits_dev + (row_index_dev ? row_index_dev[r] : r) * row_stride (the caller keeps
+ *                       the indices inside the table) and writes one int64 to out_dev[r]:
+ *       weights   w_i = exp((l_i - max_j l_j) / temp), temp > 0; -inf has weight 0 and is never returned.  A row that holds a NaN or whose
+ *                 maximum is not finite returns -1.
+ *       kept set  entries ranked by value descending, ties by ascending index (decided on the bits of the logits; -0 equals +0).
+ *                 top_k = k > 0 keeps the ranks < k; top_p = p >= 0 keeps rank j iff (the weight of the ranks < j) / (the weight of all)
+ *                 <= p, and p = 1 keeps everything; neither (top_k = 0, top_p < 0) keeps everything; both are refused.
+ *       draw      t = u * (the weight of the kept set); the result is the first kept index, in ascending index order, whose inclusive
+ *                 prefix sum of the kept weights exceeds t.  The sums are fp32: a result may differ from the exact statement where u
+ *                 lies within their rounding of an interval's end or a top-p cut lies within it of p (section 8o bounds both by 2^-18).
+ *                 Whatever the rounding, the result has a positive weight and lies in the kept set.
+ *       words     word i of the stream is mix(key + (i + 1) * 0x9E3779B97F4A7C15) (prng.py); row r uses the words 2 (offset + r), the
+ *                 mask word, and 2 (offset + r) + 1, the draw word, as u = (word >> 40) * 2^-24.  offset_dev [1] (int64), when given, is
+ *                 read by the kernel and added to `offset`: a captured graph advances the stream between replays.
+ *       mask      mask_p >= 0: row r is sampled iff u_mask < mask_p (fp32); otherwise out_dev[r] = fallback_dev[r] and the row is not read.
+ *                 mask_p < 0: every row is sampled and fallback_dev is not used.
+ * AC_EINVAL, decided on the host before the launch: a null logits_dev or out_dev; a pointer that is not aligned to its element; R < 0 or
+ * R >= 2^31; C outside 2..16384; row_stride < C; temp not finite, <= 0 or so small that 1 / temp is not finite; top_k < 0 or > C;
+ * top_p > 1 or NaN; both cuts; mask_p > 1 or NaN; mask_p >= 0 without fallback_dev.  R == 0 launches nothing.  No workspace; nothing
+ * allocates, synchronises or is read back: the call can be captured into a graph. */
+int ac_sample_form(int C);
+int ac_sample_tokens(const float* logits_dev, long long row_stride, const int64_t* row_index_dev, long long R, int C, float temp, int top_k,
+                     float top_p, uint64_t key, uint64_t offset, const int64_t* offset_dev, float mask_p, const int64_t* fallback_dev,
+                     int64_t* out_dev, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
