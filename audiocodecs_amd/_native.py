@@ -12,7 +12,7 @@ import os
 
 import torch  # noqa: F401  (loads libamdhip64 first)
 
-__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
+__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcSpkConfig", "AcSpkStages", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
            "Handle", "HandleOwner"]
 
 AC_MAX_RATIOS = 8
@@ -134,6 +134,41 @@ class AcVocosConfig(C.Structure):
     ]
 
 
+class AcSpkConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("conv_dim", C.c_int32),
+        ("num_conv_layers", C.c_int32),
+        ("conv_kernel", C.c_int32 * AC_MAX_RATIOS),
+        ("conv_stride", C.c_int32 * AC_MAX_RATIOS),
+        ("hidden_size", C.c_int32),
+        ("num_hidden_layers", C.c_int32),
+        ("num_attention_heads", C.c_int32),
+        ("intermediate_size", C.c_int32),
+        ("num_conv_pos_embeddings", C.c_int32),
+        ("num_conv_pos_embedding_groups", C.c_int32),
+        ("num_buckets", C.c_int32),
+        ("max_bucket_distance", C.c_int32),
+        ("num_tdnn_layers", C.c_int32),
+        ("tdnn_dim", C.c_int32 * AC_MAX_RATIOS),
+        ("tdnn_kernel", C.c_int32 * AC_MAX_RATIOS),
+        ("tdnn_dilation", C.c_int32 * AC_MAX_RATIOS),
+        ("xvector_output_dim", C.c_int32),
+        ("feat_extract_norm_group", C.c_int32),
+        ("conv_bias", C.c_int32),
+        ("do_stable_layer_norm", C.c_int32),
+        ("use_weighted_layer_sum", C.c_int32),
+        ("add_adapter", C.c_int32),
+        ("max_chunk_clips", C.c_int32),
+        ("device", C.c_int32),
+        ("layer_norm_eps", C.c_float),
+    ]
+
+
+class AcSpkStages(C.Structure):
+    _fields_ = [("feat", C.c_void_p), ("hidden", C.c_void_p), ("tdnn", C.c_void_p), ("pooled", C.c_void_p)]
+
+
 class AcKernelStat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 96),
@@ -240,6 +275,11 @@ EXPORTS = {
     "ac_tokstats_summary": (_i, [_vp, _i, _i, _vp, _vp]),
     "ac_sample_form": (_i, [_i]),
     "ac_sample_tokens": (_i, [_vp, _ll, _vp, _ll, _i, C.c_float, _i, C.c_float, C.c_uint64, C.c_uint64, _vp, C.c_float, _vp, _vp, _vp]),
+    "ac_spk_create": (_i, [C.POINTER(AcSpkConfig), C.POINTER(_vp)]),
+    "ac_spk_num_frames": (_i, [_ll]),
+    "ac_spk_workspace_bytes": (_sz, [_vp, _i, _ll]),
+    "ac_spk_embed": (_i, [_vp, _vp, _vp, _i, _ll, _vp, C.POINTER(AcSpkStages), _vp, _sz, _vp]),
+    "ac_spk_cosine": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

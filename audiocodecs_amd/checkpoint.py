@@ -27,7 +27,7 @@ import torch
 from . import prng
 from .config import EncodecConfig
 
-__all__ = ["conv_specs", "synthetic_state_dict", "fold_weight_norm", "mimi_conv_specs", "synthetic_mimi_state_dict", "mimi_codebook", "dac_conv_specs", "dac_snake_specs", "synthetic_dac_state_dict", "wavtok_encoder_specs", "wavtok_lstm_prefix", "synthetic_wavtok_state_dict", "synthetic_vocos_state_dict"]
+__all__ = ["conv_specs", "synthetic_state_dict", "fold_weight_norm", "mimi_conv_specs", "synthetic_mimi_state_dict", "mimi_codebook", "dac_conv_specs", "dac_snake_specs", "synthetic_dac_state_dict", "wavtok_encoder_specs", "wavtok_lstm_prefix", "synthetic_wavtok_state_dict", "synthetic_vocos_state_dict", "synthetic_wavlm_sv_state_dict"]
 
 CODEBOOK_S0 = 0.10
 CODEBOOK_RHO = 0.94
@@ -454,4 +454,66 @@ def synthetic_vocos_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
     t = t * (VOCOS_TABLE_S0 * VOCOS_TABLE_RHO ** np.arange(cfg.max_codebooks))[:, None, None]
     sd[name] = _f32(t.reshape(cfg.max_codebooks * cfg.codebook_size, cfg.input_channels))
     _vocos_backbone_and_head(sd, cfg, seed, cfg.input_channels, pos_net=False)
+    return sd
+
+
+def synthetic_wavlm_sv_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A seeded ``WavLMForXVector.state_dict()`` for `cfg` (a ``spksim.WavLMSVConfig``) in transformers' key layout, the positional conv's
+    ``parametrizations.weight.original0/1`` and the unused ``classifier.*`` / ``objective.weight`` included.  Every matrix is fan-in
+    scaled (w ~ N(0, 1 / fan_in)) and ``original0`` is the norm of ``original1`` per tap, so that activations are O(1) through the whole
+    stack: transformers' default initialisation gives embeddings of 1e-5, on which a comparison tests nothing."""
+    sd: Dict[str, torch.Tensor] = {}
+    C, H, I, heads = cfg.conv_dim, cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+
+    def mat(name, shape, fan_in, gain=1.0):
+        sd[name] = _f32(prng.normal(seed, name, shape) * (gain / np.sqrt(fan_in)))
+
+    def vec(name, n, scale=0.02):
+        sd[name] = _f32(prng.normal(seed, name, (n,)) * scale)
+
+    def linear(prefix, out, inp, gain=1.0):
+        mat(prefix + ".weight", (out, inp), inp, gain)
+        vec(prefix + ".bias", out)
+
+    def norm(prefix, n):
+        sd[prefix + ".weight"] = _f32(prng.uniform(seed, prefix + ".weight", (n,), 0.9, 1.1))
+        vec(prefix + ".bias", n)
+
+    sd["wavlm.masked_spec_embed"] = _f32(prng.uniform(seed, "wavlm.masked_spec_embed", (H,), 0.0, 1.0))
+    fx = "wavlm.feature_extractor.conv_layers."
+    for i, k in enumerate(cfg.conv_kernel):
+        cin = 1 if i == 0 else C
+        mat(f"{fx}{i}.conv.weight", (C, cin, k), cin * k, 1.4)          # (gain: GELU halves the variance)
+    norm(fx + "0.layer_norm", C)
+    norm("wavlm.feature_projection.layer_norm", C)
+    linear("wavlm.feature_projection.projection", H, C)
+    K, cg = cfg.num_conv_pos_embeddings, H // cfg.num_conv_pos_embedding_groups
+    pc = "wavlm.encoder.pos_conv_embed.conv"
+    v = _f32(prng.normal(seed, pc + ".v", (H, cg, K)) / np.sqrt(cg * K))
+    sd[pc + ".parametrizations.weight.original0"] = torch.linalg.vector_norm(v, dim=(0, 1), keepdim=True).contiguous()
+    sd[pc + ".parametrizations.weight.original1"] = v
+    vec(pc + ".bias", H)
+    norm("wavlm.encoder.layer_norm", H)
+    for l in range(cfg.num_hidden_layers):
+        p = f"wavlm.encoder.layers.{l}"
+        for nm in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            linear(f"{p}.attention.{nm}", H, H)
+        sd[f"{p}.attention.gru_rel_pos_const"] = _f32(prng.uniform(seed, p + ".gru_const", (1, heads, 1, 1), 0.8, 1.2))
+        mat(f"{p}.attention.gru_rel_pos_linear.weight", (8, H // heads), H // heads)
+        vec(f"{p}.attention.gru_rel_pos_linear.bias", 8, 0.1)
+        if l == 0:
+            sd[f"{p}.attention.rel_attn_embed.weight"] = _f32(prng.normal(seed, p + ".rel_attn_embed", (cfg.num_buckets, heads)) * 0.5)
+        norm(f"{p}.layer_norm", H)
+        linear(f"{p}.feed_forward.intermediate_dense", I, H)
+        linear(f"{p}.feed_forward.output_dense", H, I, 1.4)
+        norm(f"{p}.final_layer_norm", H)
+    sd["layer_weights"] = _f32(prng.normal(seed, "layer_weights", (cfg.num_hidden_layers + 1,)) * 0.5)
+    linear("projector", cfg.tdnn_dim[0], H)
+    for i, (d, k) in enumerate(zip(cfg.tdnn_dim, cfg.tdnn_kernel)):
+        cin = cfg.tdnn_dim[i - 1] if i > 0 else cfg.tdnn_dim[0]
+        linear(f"tdnn.{i}.kernel", d, cin * k, 1.4)
+    D = cfg.xvector_output_dim
+    linear("feature_extractor", D, 2 * cfg.tdnn_dim[-1])
+    linear("classifier", D, D)
+    mat("objective.weight", (D, 2), D)
     return sd

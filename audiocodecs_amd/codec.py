@@ -238,6 +238,15 @@ class Codec(torch.nn.Module, ABC):
         hyp = self._resynthesize(sig, length)[1]      # (the tokens go here, before the metric allocates)
         return dnsmos(hyp, self.sample_rate, weights)
 
+    def resynthesis_spk_sim(self, sig, encoder, length=None):
+        """The WavLM x-vector speaker similarity of this codec's resynthesis of `sig` [B, T] (at `self.sample_rate`) against `sig` itself:
+        `sig_to_toks`, `toks_to_sig`, the length adjustment of downstream/test_sr.py:89-100 and `speaker_similarity` (spksim.py) with a
+        `SpeakerEncoder` -- [B].  `length` also masks both signals in the encoder.  Built from the public methods only."""
+        from .spksim import speaker_similarity
+
+        hyp = self._resynthesize(sig, length)[1]      # (the tokens go here, before the metric allocates)
+        return speaker_similarity(hyp, sig.to(hyp.dtype), self.sample_rate, encoder, length)
+
     def resynthesis_report(self, sig, length=None, dnsmos_weights=None, codebook_util=None):
         """The recipe's numbers for a batch from ONE encode and ONE decode (downstream/test_sr.py:83-112): `sig_to_toks`, `toks_to_sig`, the
         length adjustment of test_sr.py:89-100 once, then `spectral_distances`, `stoi` and, with `dnsmos_weights` (a `DnsmosWeights` or the

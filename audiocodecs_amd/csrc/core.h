@@ -19,6 +19,8 @@
 //                   -- these five (knn .. tokstats) share their host side through metric_host.h: the pointer alignment rule, the status behind the
 //                   launches, the octant-reduced cosine, the triangular filterbank and the workspace cursor; the fp64 ->
 //                   fp16-pair split of their table kernels is s16_split64 (split16.h)
+//   spk_path.hip    the WavLM x-vector speaker encoder (wavlm.h): plan, finalize, the launch sequence of one embedding call, its kernels and the
+//                   ac_spk_* entry points
 //   ac_api.hip    the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
@@ -151,6 +153,27 @@ struct WavtokPlan {
     int tables = 1;
 };
 
+struct SpkTfLayer {
+    PackedGemm qkv, o, fc1, fc2;                       // [3H][H] (q | k | v), [H][H], [I][H], [H][I]; all with biases
+    size_t ln1_w = 0, ln1_b = 0, ln2_w = 0, ln2_b = 0;
+    size_t gate_w = 0, gate_b = 0, gate_c = 0;         // gru_rel_pos_linear [8][64], its bias [8], gru_rel_pos_const [heads]
+};
+
+struct SpkPlan {                                       // spk_path.hip: WavLM x-vector speaker encoder
+    size_t stem_w = 0, gn_w = 0, gn_b = 0;             // conv 1 [C][10], its GroupNorm
+    std::vector<PackedGemm> conv;                      // convs 2..7 (k3 / s2 packed with a zero fourth tap)
+    size_t fp_ln_w = 0, fp_ln_b = 0, enc_ln_w = 0, enc_ln_b = 0;
+    PackedGemm fp;                                     // feature projection [H][C]
+    size_t pos_img = 0, pos_inv = 0, pos_b = 0;        // positional conv: Packer::frag16 image of [H][k * H/groups], 2^-s, bias
+    std::vector<SpkTfLayer> tf;
+    size_t bias_tab = 0;                               // [heads][2 R + 1]: layer 0's rel_attn_embed at the bucket of every offset
+    int R = 0;
+    std::vector<float> lw;                             // softmax(layer_weights)
+    PackedGemm proj, fe;
+    std::vector<PackedGemm> tdnn;
+    int shrink = 0;                                    // rows the TDNN stack drops: sum (k - 1) * dilation
+};
+
 struct ProfRec {
     int name_id;
     int count;
@@ -162,7 +185,7 @@ struct ProfRec {
 }  // namespace acimpl
 using namespace acimpl;
 
-enum { ARCH_ENCODEC = 0, ARCH_MIMI = 1, ARCH_DAC = 2, ARCH_WAVTOK = 3 };
+enum { ARCH_ENCODEC = 0, ARCH_MIMI = 1, ARCH_DAC = 2, ARCH_WAVTOK = 3, ARCH_SPK = 4 };
 
 struct ac_handle {
     int arch = ARCH_ENCODEC;
@@ -173,6 +196,8 @@ struct ac_handle {
     DacPlan dac;
     ac_wavtok_config wcfg{};
     WavtokPlan wt;
+    ac_spk_config scfg{};
+    SpkPlan spk;
     std::string err;
     std::map<std::string, std::vector<float>> host;
     bool finalized = false;
@@ -1084,6 +1109,7 @@ int dac_from_codes(ac_handle* h, hipStream_t st, const long long* toks, int F, i
 int wavtok_finalize(ac_handle* h, Packer& pk);
 Workspace wavtok_plan_ws(const ac_handle* h, int B, int T_in, int N_frames, bool enc);
 int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, int N, float* sig, WsPtrs& ws);
+int spk_finalize(ac_handle* h, Packer& pk);             // spk_path.hip
 int upload_blob(ac_handle* h, Packer& pk, int device);
 constexpr int DAC_CODE_DIM = 8;   // = DAC_D (dac.h), asserted in dac_path.hip
 

@@ -705,6 +705,72 @@ int ac_sample_tokens(const float* logits_dev, long long row_stride, const int64_
                      float top_p, uint64_t key, uint64_t offset, const int64_t* offset_dev, float mask_p, const int64_t* fallback_dev,
                      int64_t* out_dev, void* stream);
 
+/* WavLM x-vector speaker embeddings: inference of transformers' WavLMForXVector for the microsoft/wavlm-base-sv
+ * family on one more ac_handle kind -- 7-layer conv front end (GroupNorm over time behind the first), feature projection, grouped
+ * positional conv, post-LN transformer layers with gated relative-position bias and key padding, weighted layer sum, projector, TDNN
+ * layers, statistic pooling, feature_extractor.  Weights go in through ac_load_weights under their WavLMForXVector state-dict names
+ * (classifier.* and objective.* are accepted and unused; the positional conv's weight norm -- over dims (0, 1), one norm per tap --
+ * is folded on the host at ac_finalize unless wavlm.encoder.pos_conv_embed.conv.weight itself is loaded) plus "spk.bucket_table", the
+ * relative-position buckets of the offsets
+ * -2 max_distance .. 2 max_distance as floats (2 * 2 * max_distance + 1 values, built by the caller with the backend's own fp32
+ * operations: the table is data).
+ *   ac_spk_create          AC_EINVAL for anything but feat_extract_norm "group", no conv bias, post-LN layers, the weighted layer sum, no
+ *                          adapter, head dim 64, conv kernels (10,3,3,3,3,2,2) with strides (5,2,2,2,2,2,2), and widths the kernels take
+ *                          (conv_dim % 32, hidden % 64, per-group width of the positional conv % 16, TDNN kernels summing to
+ *                          receptive field 15); decided before a device is looked for.
+ *   ac_spk_num_frames(L)   (L - 400) / 320 + 1 frames of a clip of L samples at 16 kHz (0 below 400 samples); handle-free.
+ *   ac_spk_workspace_bytes workspace of one ac_spk_embed call: the batch is walked in chunks of max_chunk_clips clips (0: as many as keep
+ *                          the workspace under 1 GiB, at least one), so the size stops growing with B.
+ *   ac_spk_embed           sig16k_dev [B][L] fp32 at 16 kHz, raw (no normalisation).  valid_dev [B] int32 or NULL: the samples of clip b
+ *                          that are speech; frames t >= Lf = (valid - 400) / 320 + 1 are zeroed behind the feature projection and masked as
+ *                          attention keys, and the rows [0, min(Lf - 8, T - 14)) are pooled (NULL: all T - 14).  The lengths are read on
+ *                          the device: the call copies nothing back.  A clip with one pooled row has a NaN embedding (unbiased std of one
+ *                          row, as in the backend); with none, also NaN.  L < 4880 (T < 15: no pooled row at all) is AC_EINVAL.
+ *                          emb_out [B][xvector_dim].  stages: optional outputs, each pointer may be NULL.
+ *   ac_spk_cosine          out[b] = <a_b, b_b> / (max(|a_b|, eps) max(|b_b|, eps)), eps 1e-8 (torch.nn.functional.cosine_similarity), one
+ *                          wave per pair; handle-free.
+ * Results of a clip do not depend on the clips beside it or on the chunking. */
+typedef struct ac_spk_config {
+    int32_t struct_size;
+    int32_t conv_dim;                       /* width of all conv layers (512)                      */
+    int32_t num_conv_layers;                /* 7                                                   */
+    int32_t conv_kernel[AC_MAX_RATIOS];     /* (10,3,3,3,3,2,2)                                    */
+    int32_t conv_stride[AC_MAX_RATIOS];     /* (5,2,2,2,2,2,2)                                     */
+    int32_t hidden_size;                    /* 768                                                 */
+    int32_t num_hidden_layers;              /* 12                                                  */
+    int32_t num_attention_heads;            /* 12                                                  */
+    int32_t intermediate_size;              /* 3072                                                */
+    int32_t num_conv_pos_embeddings;        /* 128                                                 */
+    int32_t num_conv_pos_embedding_groups;  /* 16                                                  */
+    int32_t num_buckets;                    /* 320                                                 */
+    int32_t max_bucket_distance;            /* 800                                                 */
+    int32_t num_tdnn_layers;                /* 5                                                   */
+    int32_t tdnn_dim[AC_MAX_RATIOS];        /* (512,512,512,512,1500)                              */
+    int32_t tdnn_kernel[AC_MAX_RATIOS];     /* (5,3,3,1,1)                                         */
+    int32_t tdnn_dilation[AC_MAX_RATIOS];   /* (1,2,3,1,1)                                         */
+    int32_t xvector_output_dim;             /* 512                                                 */
+    int32_t feat_extract_norm_group;        /* 1: "group" (the only variant)                       */
+    int32_t conv_bias;                      /* 0                                                   */
+    int32_t do_stable_layer_norm;           /* 0                                                   */
+    int32_t use_weighted_layer_sum;         /* 1                                                   */
+    int32_t add_adapter;                    /* 0                                                   */
+    int32_t max_chunk_clips;                /* clips per pass over the stack; 0: from the 1 GiB cap */
+    int32_t device;
+    float layer_norm_eps;                   /* 1e-5                                                */
+} ac_spk_config;
+typedef struct ac_spk_stages {
+    float* feat;      /* [B][T][conv_dim]                 output of the last conv layer                                    */
+    float* hidden;    /* [layers + 1][B][T][hidden]       the input of every layer, then the last layer's output           */
+    float* tdnn;      /* [B][T - 14][tdnn_dim[last]]      output of the last TDNN layer                                    */
+    float* pooled;    /* [B][2 * tdnn_dim[last]]          mean | unbiased std over the clip's pooled rows                  */
+} ac_spk_stages;
+int ac_spk_create(const ac_spk_config* cfg, ac_handle** out);
+int ac_spk_num_frames(long long L);
+size_t ac_spk_workspace_bytes(const ac_handle* h, int B, long long L);
+int ac_spk_embed(ac_handle* h, const float* sig_dev, const int32_t* valid_dev, int B, long long L, float* emb_out, const ac_spk_stages* stages,
+                 void* ws, size_t ws_bytes, void* stream);
+int ac_spk_cosine(const float* a_dev, const float* b_dev, int B, int D, float* out_dev, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
