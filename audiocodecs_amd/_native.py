@@ -12,7 +12,7 @@ import os
 
 import torch  # noqa: F401  (loads libamdhip64 first)
 
-__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcSpkConfig", "AcSpkStages", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
+__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcSpkConfig", "AcSpkStages", "AcLmConfig", "AcLmLayout", "AcLmStages", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
            "Handle", "HandleOwner"]
 
 AC_MAX_RATIOS = 8
@@ -169,6 +169,32 @@ class AcSpkStages(C.Structure):
     _fields_ = [("feat", C.c_void_p), ("hidden", C.c_void_p), ("tdnn", C.c_void_p), ("pooled", C.c_void_p)]
 
 
+class AcLmConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("vocab_size", C.c_int32),
+        ("n_layers", C.c_int32),
+        ("dim", C.c_int32),
+        ("ffn_dim", C.c_int32),
+        ("n_heads", C.c_int32),
+        ("n_kv_heads", C.c_int32),
+        ("max_seq_len", C.c_int32),
+        ("prompt_dim", C.c_int32),
+        ("num_codebooks", C.c_int32),
+        ("device", C.c_int32),
+        ("norm_eps", C.c_float),
+        ("rope_theta", C.c_float),
+    ]
+
+
+class AcLmLayout(C.Structure):
+    _fields_ = [(k, C.c_longlong) for k in ("hdr", "alive", "lens", "tok", "logits", "hyp", "kv", "plane_bytes", "total")]
+
+
+class AcLmStages(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("attn", C.c_void_p), ("layer_out", C.c_void_p), ("final_norm", C.c_void_p)]
+
+
 class AcKernelStat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 96),
@@ -280,6 +306,14 @@ EXPORTS = {
     "ac_spk_workspace_bytes": (_sz, [_vp, _i, _ll]),
     "ac_spk_embed": (_i, [_vp, _vp, _vp, _i, _ll, _vp, C.POINTER(AcSpkStages), _vp, _sz, _vp]),
     "ac_spk_cosine": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ac_lm_create": (_i, [C.POINTER(AcLmConfig), C.POINTER(_vp)]),
+    "ac_lm_state_layout": (_i, [_vp, _i, _i, _i, C.POINTER(AcLmLayout)]),
+    "ac_lm_state_bytes": (_sz, [_vp, _i, _i, _i]),
+    "ac_lm_reset": (_i, [_vp, _vp, _sz, _i, _i, _i, _ll, _vp]),
+    "ac_lm_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "ac_lm_embed": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "ac_lm_forward": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp, _i, _vp, C.POINTER(AcLmStages), _vp, _sz, _vp]),
+    "ac_lm_step": (_i, [_vp, _vp, _sz, _i, _i, _i, _ll, C.c_float, C.c_float, C.c_uint64, _vp, _vp, _sz, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

@@ -21,6 +21,8 @@
 //                   fp16-pair split of their table kernels is s16_split64 (split16.h)
 //   spk_path.hip    the WavLM x-vector speaker encoder (wavlm.h): plan, finalize, the launch sequence of one embedding call, its kernels and the
 //                   ac_spk_* entry points
+//   lm_path.hip     the Llama decoder with a KV cache (llama.h): plan, finalize, the state's layout, the launch sequences of a forward and of one
+//                   generated token, its kernels and the ac_lm_* entry points; the token draw goes through the public ac_sample_tokens
 //   ac_api.hip    the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
@@ -174,6 +176,16 @@ struct SpkPlan {                                       // spk_path.hip: WavLM x-
     int shrink = 0;                                    // rows the TDNN stack drops: sum (k - 1) * dilation
 };
 
+struct LmLayer {
+    size_t an = 0, fn = 0, wqkv = 0, wo = 0, w1 = 0, w3 = 0, w2 = 0;   // the two norm weights; [nq + 2 nkv hd][dim] (q | k | v), [dim][nq], [ffn][dim] x 2, [dim][ffn]; fp32, no biases
+};
+
+struct LmPlan {                                        // lm_path.hip: Llama decoder with a KV cache
+    size_t emb = 0, prompt = 0, norm = 0, head = 0;    // [codebooks * vocab][dim], [dim][prompt_dim], [dim], [codebooks][vocab][dim]
+    size_t rope_cos = 0, rope_sin = 0;                 // [2 * max_seq_len][head_dim / 2]: the caller's table
+    std::vector<LmLayer> layers;
+};
+
 struct ProfRec {
     int name_id;
     int count;
@@ -185,7 +197,7 @@ struct ProfRec {
 }  // namespace acimpl
 using namespace acimpl;
 
-enum { ARCH_ENCODEC = 0, ARCH_MIMI = 1, ARCH_DAC = 2, ARCH_WAVTOK = 3, ARCH_SPK = 4 };
+enum { ARCH_ENCODEC = 0, ARCH_MIMI = 1, ARCH_DAC = 2, ARCH_WAVTOK = 3, ARCH_SPK = 4, ARCH_LM = 5 };
 
 struct ac_handle {
     int arch = ARCH_ENCODEC;
@@ -198,6 +210,8 @@ struct ac_handle {
     WavtokPlan wt;
     ac_spk_config scfg{};
     SpkPlan spk;
+    ac_lm_config lcfg{};
+    LmPlan lm;
     std::string err;
     std::map<std::string, std::vector<float>> host;
     bool finalized = false;
@@ -1110,6 +1124,7 @@ int wavtok_finalize(ac_handle* h, Packer& pk);
 Workspace wavtok_plan_ws(const ac_handle* h, int B, int T_in, int N_frames, bool enc);
 int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, int N, float* sig, WsPtrs& ws);
 int spk_finalize(ac_handle* h, Packer& pk);             // spk_path.hip
+int lm_finalize(ac_handle* h, Packer& pk);              // lm_path.hip
 int upload_blob(ac_handle* h, Packer& pk, int device);
 constexpr int DAC_CODE_DIM = 8;   // = DAC_D (dac.h), asserted in dac_path.hip
 

@@ -771,6 +771,72 @@ int ac_spk_embed(ac_handle* h, const float* sig_dev, const int32_t* valid_dev, i
                  void* ws, size_t ws_bytes, void* stream);
 int ac_spk_cosine(const float* a_dev, const float* b_dev, int B, int D, float* out_dev, void* stream);
 
+/* The Llama decoder with a KV cache: inference of the downstream recipes' LlamaDecoder (RMSNorm, grouped-query
+ * attention with rotary embeddings on interleaved pairs, SwiGLU feed-forward, one output head per codebook) and its token generation
+ * loop on one more ac_handle kind.  fp32 weights, fp32 FMAs.  Weights go in through ac_load_weights under the model's state-dict names
+ * (tok_embeddings.weight, layers.N.attention.{wq,wk,wv,wo}.weight, layers.N.attention_norm.weight, layers.N.feed_forward.{w1,w2,w3}.weight,
+ * layers.N.ffn_norm.weight, norm.weight, output.weight or output.K.weight, prompt.weight) plus "lm.rope_cos" and "lm.rope_sin"
+ * [2 * max_seq_len][head_dim / 2]: cos and sin of the rotary angles, built by the caller with the model's own fp32 operations (the
+ * table is data; no kernel recomputes an angle).
+ *   A STATE is a caller-owned, 256-byte aligned device buffer of ac_lm_state_bytes(B, capacity, max_steps) bytes: 64 header words
+ *   (position, step counter, overflow flag, draw offset), alive / lens per row, the sampler's tokens, the pending logits [B][vocab] of
+ *   the last row, hyp [B][max_steps] int64 and per layer the K and V planes [B][capacity][n_kv_heads][head_dim] (ac_lm_state_layout
+ *   gives the byte offsets).  The position lives on the device; no call reads it back.
+ *   ac_lm_create           AC_EINVAL unless dim % n_heads == 0, n_heads % n_kv_heads == 0 with 1, 2, 4 or 8 query heads per key/value
+ *                          head, an even head dim <= 256, dim, ffn_dim and prompt_dim multiples of 4, 2 <= vocab_size <= 16384 (the
+ *                          sampler's range); decided before a device is looked for.  prompt_dim 0: no prompt projection.
+ *   ac_lm_reset            position 0, step 0, every row alive, the draw offset `offset`; B <= 64 rows, capacity <= 2 * max_seq_len.
+ *   ac_lm_embed            out [B][P + T][dim]: P prompt rows (projected by prompt.weight when prompt_width == prompt_dim, copied when
+ *                          it is dim) followed by the rows of toks [B][T] int64: token j reads row tok + ((curr_pos + j) % num_codebooks)
+ *                          * vocab_size of the table.  Ids are clamped into the table.
+ *   ac_lm_forward          appends the T rows embs [B][T][dim] at the state's position, which has to be `pos` (the host's copy), and leaves
+ *                          the last row's logits pending in the state; logits_out [B][T][vocab] or NULL; the row at absolute position
+ *                          p uses output head p % num_codebooks.  pos + T > capacity is AC_EINVAL and leaves the state untouched.
+ *   ac_lm_step             one generated token: draws row r from the pending logits with ac_sample_tokens' top-p rule (top_p 0: argmax)
+ *                          at element offset + step * B + r of the stream `key`; hyp[:, step] = tok; alive &= tok != eos_id; lens += alive;
+ *                          then runs the layers on embed(tok, curr_pos = step + 1) for the next pending logits.  logits_log
+ *                          [max_steps][B][vocab] or NULL receives the logits every token was drawn from.  Everything is read from the
+ *                          state: a captured step replays without new arguments.  Steps behind max_steps, or behind the step in which the
+ *                          last row ended, change nothing.  A step whose position would pass the capacity writes nothing and raises the
+ *                          header's flag word (word 4), which the caller polls. */
+typedef struct ac_lm_config {
+    int32_t struct_size;
+    int32_t vocab_size;        /* ids per codebook = logits per row (1026)   */
+    int32_t n_layers;          /* 12                                         */
+    int32_t dim;               /* 512                                        */
+    int32_t ffn_dim;           /* 2048                                       */
+    int32_t n_heads;           /* 4                                          */
+    int32_t n_kv_heads;        /* 1                                          */
+    int32_t max_seq_len;       /* 8192: the rotary table has twice as many rows */
+    int32_t prompt_dim;        /* 0: none                                    */
+    int32_t num_codebooks;     /* 2                                          */
+    int32_t device;
+    float norm_eps;            /* 1e-6                                       */
+    float rope_theta;          /* 10000 (informative: the table is loaded)   */
+} ac_lm_config;
+typedef struct ac_lm_layout {  /* byte offsets into a state */
+    long long hdr, alive, lens, tok, logits, hyp, kv;
+    long long plane_bytes;     /* layer l: K at kv + 2 l plane_bytes, V one plane behind it */
+    long long total;
+} ac_lm_layout;
+typedef struct ac_lm_stages {  /* optional outputs of ac_lm_forward, each pointer may be NULL */
+    float* q;            /* [layers][B][T][n_heads * head_dim]   rotated queries                  */
+    float* attn;         /* [layers][B][T][n_heads * head_dim]   attention output (before wo)     */
+    float* layer_out;    /* [layers][B][T][dim]                  the layer's output               */
+    float* final_norm;   /* [B][T][dim]                          the final RMSNorm                */
+} ac_lm_stages;
+int ac_lm_create(const ac_lm_config* cfg, ac_handle** out);
+int ac_lm_state_layout(const ac_handle* h, int B, int capacity, int max_steps, ac_lm_layout* out);
+size_t ac_lm_state_bytes(const ac_handle* h, int B, int capacity, int max_steps);
+int ac_lm_reset(ac_handle* h, void* state_dev, size_t state_bytes, int B, int capacity, int max_steps, long long offset, void* stream);
+size_t ac_lm_workspace_bytes(const ac_handle* h, int B, int T, int capacity);
+int ac_lm_embed(ac_handle* h, const int64_t* toks_dev, int B, int T, int curr_pos, const float* prompt_dev, int P, int prompt_width, float* out_dev,
+                void* stream);
+int ac_lm_forward(ac_handle* h, void* state_dev, size_t state_bytes, int B, int capacity, int max_steps, int pos, const float* embs_dev, int T,
+                  float* logits_out, const ac_lm_stages* stages, void* ws, size_t ws_bytes, void* stream);
+int ac_lm_step(ac_handle* h, void* state_dev, size_t state_bytes, int B, int capacity, int max_steps, long long eos_id, float temp, float top_p,
+               uint64_t key, float* logits_log, void* ws, size_t ws_bytes, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
