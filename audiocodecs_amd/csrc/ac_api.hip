@@ -356,7 +356,7 @@ int ac_encode(ac_handle* h, const float* sig, const float* rel_len, int B, int T
         rc = mimi_encoder_fwd(h, st, sig, B, T, feats, p);
         if (rc) return rc;
         float* proj = p.take();
-        rc = mimi_linear(h, st, h->mimi.in_proj, feats, (long long)B * N, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
+        rc = linear_rows(h, st, h->mimi.in_proj, feats, (long long)B * N, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
         if (rc) return rc;
         return mimi_rvq_encode(h, st, proj, B * N, K, reinterpret_cast<long long*>(toks));
     }
@@ -381,7 +381,7 @@ int ac_quantize_ws(ac_handle* h, const float* feats, int B, int N, int K, int64_
         if (!ws || ws_bytes < ac_quantizer_workspace_bytes(h, B, N)) return fail(h, AC_ENOMEM, "ac_quantize: workspace missing or too small");
         float* proj = quantizer_scratch(h, ws, B, N);
         if ((rc = amax_begin(h, (hipStream_t)stream, 1))) return rc;
-        rc = mimi_linear(h, (hipStream_t)stream, h->mimi.in_proj, feats, (long long)B * N, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
+        rc = linear_rows(h, (hipStream_t)stream, h->mimi.in_proj, feats, (long long)B * N, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
         if (rc) return rc;
         return mimi_rvq_encode(h, (hipStream_t)stream, proj, B * N, K, reinterpret_cast<long long*>(toks));
     }
@@ -512,7 +512,7 @@ int ac_embs_projected(ac_handle* h, int K, float* embs, void* stream) {
     if ((rc = amax_begin(h, (hipStream_t)stream, 1))) return rc;
     for (int q = 0; q < K; ++q) {
         const int part = q < c.num_semantic_quantizers ? 0 : 1;
-        rc = mimi_linear(h, (hipStream_t)stream, h->mimi.out_proj, h->blob + h->mimi.cb_plain + (size_t)q * c.codebook_size * c.codebook_dim,
+        rc = linear_rows(h, (hipStream_t)stream, h->mimi.out_proj, h->blob + h->mimi.cb_plain + (size_t)q * c.codebook_size * c.codebook_dim,
                          c.codebook_size, c.codebook_dim, c.codebook_dim, part * c.codebook_dim,
                          embs + (size_t)q * c.codebook_size * c.hidden_size, c.hidden_size);
         if (rc) return rc;

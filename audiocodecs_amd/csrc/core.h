@@ -1,6 +1,8 @@
 // Host-side internals shared by the translation units of libaudiocodecs_amd.so:
-//   core.hip        the shared machinery (weight packing, split16 pools, tap-GEMM dispatch (its kernel choice: tap_route.h), fused-block / LSTM / codebook launchers,
-//                   workspace planning) and the EnCodec encoder / decoder; owns every kernel the codecs share
+//   core.hip        the shared machinery (weight packing, split16 pools, the tap-GEMM call path -- tap_layer maps a packed layer, its operand
+//                   segments, destination and epilogue terms onto TapGemmParams for every caller in the library; run_tap dispatches (its kernel
+//                   choice: tap_route.h) --, linear_rows, fused-block / LSTM / codebook launchers, workspace planning) and the EnCodec
+//                   encoder / decoder; owns every kernel the codecs share
 //   mimi_path.hip, dac_path.hip, wavtok_path.hip   one codec each: plan, finalize, forward passes, its own kernels, its ac_*_create
 //   mimi_stream.hip streaming Mimi encode and decode: the stream states, one push's launch sequence, its kernels and the ac_mimi_stream_* entry points
 //   encodec_stream.hip streaming EnCodec encode and decode: the stream states (conv histories, the LSTM's h and c), one push's launch sequence,
@@ -34,6 +36,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -942,8 +945,6 @@ TapSeg make_seg(const Act& x, int s, int J, int pad /*PAD_**/, int extra, int ko
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p);
-
 
 // What a layer should produce: the raw output, its ELU, or both (SEANet consumers all start with ELU;
 // shortcuts, LSTMs and the public outputs want the raw value).
@@ -955,6 +956,48 @@ struct Out {
 struct Act2 {       // a layer output in up to two flavours (same shape/strides)
     Act raw{}, elu{};
 };
+
+// the two flavours of one output: the same strides, shape and amax word for B clips, each on its own buffer (either may be null)
+inline Act2 act_pair(Out o, long long bs, long long ts, int L, int C, const unsigned* amax, int B) {
+    return Act2{Act{o.raw, bs, ts, L, C, amax, B}, Act{o.elu, bs, ts, L, C, amax, B}};
+}
+
+// optional epilogue terms of a tap-GEMM launch (TapGemmParams has the arithmetic of each)
+struct Epi {
+    const float* scale = nullptr;
+    const float* res = nullptr;
+    long long res_bs = 0, res_rs = 0;
+    int gelu = 0;
+    const float* alpha = nullptr;       // DAC: the activated flavour is Snake (per channel n % alpha_n) instead of ELU
+    const float* alpha_inv = nullptr;
+    int alpha_n = 0;
+    int tanh_out = 0;
+    bool no_bias = false;               // the layer's bias is withheld: its consumer adds it (the streamed LSTM's step kernel)
+    // split16.h row mode (a linear layer over a merged row matrix: B = 1, one segment, one tap): every row scales by its own amax.
+    // rowmax_in: per-row amax words of the input when its producer left them (linear_rows puts them on the segment);
+    // rowmax_out: where to return the output's (null: not wanted)
+    bool row_mode = false;
+    const unsigned* rowmax_in = nullptr;
+    const unsigned** rowmax_out = nullptr;
+};
+
+// where a tap-GEMM's rows go, and the view of them its consumer receives
+struct TapDst {
+    Out out;
+    long long bs = 0, rs = 0;           // floats between clips / between the GEMM's output rows of g.N floats
+    int L = 0, C = 0;                   // the consumer's view when it is not [M][g.N] at (bs, rs): L time steps of C channels, C floats
+                                        //   apart (a transposed conv's row of s * cout floats is s time steps of cout)
+    long long y_off = 0, y_len = 0;     // TapGemmParams::y_off / y_len
+    int n_valid = 0;                    // TapGemmParams::n_valid
+};
+
+// The one way a packed layer reaches the tap-GEMM (core.hip): maps (g, segments, destination, epilogue) onto TapGemmParams, runs run_tap and,
+// on success, hands the consumer's view -- with the output's amax word -- back through `y` (null: not wanted)
+int tap_layer(ac_handle* h, hipStream_t st, const PackedGemm& g, std::initializer_list<TapSeg> segs, int B, int M, const TapDst& d,
+              const Epi& epi = Epi{}, Act2* y = nullptr);
+
+// taps of a conv as the tap-GEMM runs it: k at stride 1, two rows of s time steps at k = 2*stride; every other shape is refused
+int conv_taps(ac_handle* h, int k, int s, int* J);
 
 int try_thin6(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, int width, int edge, Out out, int B, const unsigned** amax_out = nullptr);
 
@@ -1085,27 +1128,17 @@ int resample_stream_push_slots_launch(void* state, int B, const int* slots_dev, 
                                       int L, const float* kern, int n, int o, int taps, int width, float* y, long long y_pitch, int m, int finish,
                                       hipStream_t st);
 
-// ---- per-codec paths (mimi_path.hip, dac_path.hip, wavtok_path.hip)
-// optional epilogue terms of a tap-GEMM launch (Mimi's transformers, WavTokenizer's backbone, DAC's residual units)
-struct Epi {
-    const float* scale = nullptr;
-    const float* res = nullptr;
-    long long res_bs = 0, res_rs = 0;
-    int gelu = 0;
-    // split16.h row mode (mimi_linear): per-row amax words of the input when the producing linear layer left them, and
-    // where to return the output's (null: not wanted)
-    const unsigned* rowmax_in = nullptr;
-    const unsigned** rowmax_out = nullptr;
-};
+// y[rows][N] = epi(x[rows][cin-slice] * W^T): a 1-tap row-mode GEMM over a merged row matrix (core.hip; the transformers of Mimi and
+// the speaker encoder, WavTokenizer's and Vocos' backbone, the quantisers' projections)
+int linear_rows(ac_handle* h, hipStream_t st, const PackedGemm& g, const float* x, long long rows, int cin, int x_pitch, int kofs,
+                float* y, int y_pitch, const Epi& epi = Epi{});
 
+// ---- per-codec paths (mimi_path.hip, dac_path.hip, wavtok_path.hip)
 int mimi_finalize(ac_handle* h, Packer& pk);
 Workspace mimi_plan_ws(const ac_handle* h, int B, int T_in, int N_frames, bool enc);
 int mimi_num_frames25(const ac_mimi_config& c, long long T);
 int mimi_encoder_fwd(ac_handle* h, hipStream_t st, const float* sig, int B, int T, float* feats, WsPtrs& ws);
 int mimi_decoder_fwd(ac_handle* h, hipStream_t st, const float* qfeats, int B, int N, float* sig, WsPtrs& ws);
-// y[rows][N] = epi(x[rows][cin-slice] * W^T): a 1-tap GEMM over a merged token matrix (core.hip; Mimi and WavTokenizer use it)
-int mimi_linear(ac_handle* h, hipStream_t st, const PackedGemm& g, const float* x, long long rows, int cin, int x_pitch, int kofs,
-                float* y, int y_pitch, const Epi& epi = Epi{});
 int layernorm_fwd(ac_handle* h, hipStream_t st, const float* x, size_t w_off, size_t b_off, float* y, long long rows, int H, float eps,
                   const unsigned** rows_out = nullptr);   // mimi_path.hip
 int mimi_rvq_encode(ac_handle* h, hipStream_t st, const float* proj, int F, int K, long long* toks);

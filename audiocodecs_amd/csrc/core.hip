@@ -319,8 +319,8 @@ TapSeg make_seg(const Act& x, int s, int J, int pad /*PAD_**/, int extra, int ko
 
 
 // Every conv / linear layer: route_tap picks the kernel, then the split16 operands it needs get their amax slots / row words (in
-// launch order: the slots come out in the same sequence run to run), then the family's launcher runs it.
-int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p) {
+// launch order: the slots come out in the same sequence run to run), then the family's launcher runs it.  tap_layer is its one caller.
+static int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p) {
     const auto w6_it = h->w6_of.find((size_t)(p.w - h->blob));
     const auto iv = h->winv_of.find((size_t)(p.w - h->blob));
     TapRouteInputs in;
@@ -393,6 +393,50 @@ int run_tap(ac_handle* h, hipStream_t st, TapGemmParams& p) {
 }
 
 
+// The one mapping of a packed layer, its operand segments, its destination and its epilogue terms onto TapGemmParams.  What a caller
+// knows about its layer (padding, dilation, the consumer's view of a transposed conv's rows) arrives in the segments and in `d`.
+int tap_layer(ac_handle* h, hipStream_t st, const PackedGemm& g, std::initializer_list<TapSeg> segs, int B, int M, const TapDst& d, const Epi& epi,
+              Act2* y) {
+    if (segs.size() < 1 || segs.size() > 2) return fail(h, AC_EINVAL, "tap_layer: %zu operand segments (one or two)", segs.size());
+    TapGemmParams p{};
+    for (const TapSeg& sg : segs) p.seg[p.nseg++] = sg;
+    p.w = h->blob + g.w_off;
+    p.bias = g.has_bias && !epi.no_bias ? h->blob + g.b_off : nullptr;
+    p.y = d.out.raw;
+    p.y_elu = d.out.elu;
+    p.y_bs = d.bs;
+    p.y_rs = d.rs;
+    p.y_off = d.y_off;
+    p.y_len = d.y_len;
+    p.n_valid = d.n_valid;
+    p.B = B;
+    p.M = M;
+    p.N = g.N;
+    p.Ktot = g.Ktot;
+    p.scale = epi.scale;
+    p.res = epi.res;
+    p.res_bs = epi.res_bs;
+    p.res_rs = epi.res_rs;
+    p.gelu = epi.gelu;
+    p.alpha = epi.alpha;
+    p.alpha_inv = epi.alpha_inv;
+    p.alpha_n = epi.alpha_n;
+    p.tanh_out = epi.tanh_out;
+    p.amax_rows = epi.row_mode ? 1 : 0;
+    if (epi.rowmax_out) p.amax_out_rows = reinterpret_cast<unsigned*>(1);   // request; run_tap allocates
+    if (int rc = run_tap(h, st, p)) return rc;
+    if (epi.rowmax_out) *epi.rowmax_out = p.amax_out_rows;
+    if (y) *y = d.L ? act_pair(d.out, d.bs, d.C, d.L, d.C, p.amax_out, B) : act_pair(d.out, d.bs, d.rs, M, g.N, p.amax_out, B);
+    return AC_OK;
+}
+
+int conv_taps(ac_handle* h, int k, int s, int* J) {
+    if (s != 1 && k != 2 * s) return fail(h, AC_EINVAL, "strided conv needs kernel == 2*stride (got k=%d, s=%d)", k, s);
+    *J = s == 1 ? k : 2;
+    return AC_OK;
+}
+
+
 // the [64][128] layers on 64-float super-rows (thin_conv6.h); returns 1 when the shape does not qualify
 int try_thin6(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, int width, int edge, Out out, int B, const unsigned** amax_out) {
     if (h->gemm_fp32 || g.N != 64 || g.Ktot != 128 || x.C != width || x.ts != width || x.bs != (long long)x.L * width ||
@@ -437,39 +481,19 @@ int conv_fwd(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, in
         const unsigned* am = nullptr;
         const int rc = try_thin6(h, st, g, x, 32, 1, out, B, &am);
         if (rc <= 0) {
-            if (y && !rc) {
-                y->raw = Act{out.raw, out_bs, out_rs, M, g.N, am, B};
-                y->elu = Act{out.elu, out_bs, out_rs, M, g.N, am, B};
-            }
+            if (y && !rc) *y = act_pair(out, out_bs, out_rs, M, g.N, am, B);
             if (!rc) HIPCHK(h, hipGetLastError());
             return rc;
         }
     }
-    TapGemmParams p{};
-    p.nseg = 1;
-    if (s != 1 && k != 2 * s) return fail(h, AC_EINVAL, "strided conv needs kernel == 2*stride (got k=%d, s=%d)", k, s);
+    int J;
+    if (int rc = conv_taps(h, k, s, &J)) return rc;
+    int left = -1, right = 0;
     if (h->noncausal) {   // padding_total = k - s; right = total / 2, left = total - right
-        const int total = k - s, right = total / 2;
-        p.seg[0] = make_seg(x, s, s == 1 ? k : 2, PAD_REFLECT, extra, 0, rel_len, total - right, right);
-    } else {
-        p.seg[0] = make_seg(x, s, s == 1 ? k : 2, PAD_REFLECT, extra, 0, rel_len);
+        right = (k - s) / 2;
+        left = k - s - right;
     }
-    p.w = h->blob + g.w_off;
-    p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
-    p.y = out.raw;
-    p.y_elu = out.elu;
-    p.y_bs = out_bs;
-    p.y_rs = out_rs;
-    p.B = B;
-    p.M = M;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    const int rc = run_tap(h, st, p);
-    if (y) {
-        y->raw = Act{out.raw, out_bs, out_rs, M, g.N, p.amax_out, p.B};
-        y->elu = Act{out.elu, out_bs, out_rs, M, g.N, p.amax_out, p.B};
-    }
-    return rc;
+    return tap_layer(h, st, g, {make_seg(x, s, J, PAD_REFLECT, extra, 0, rel_len, left, right)}, B, M, TapDst{out, out_bs, out_rs}, Epi{}, y);
 }
 
 
@@ -480,30 +504,14 @@ int convtr_fwd(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, 
         const int rc = try_thin6(h, st, g, x, 64, 0, out, B, &am);
         if (rc <= 0) {
             if (!rc) {
-                y->raw = Act{out.raw, (long long)x.L * s * cout, cout, x.L * s, cout, am, B};
-                y->elu = Act{out.elu, (long long)x.L * s * cout, cout, x.L * s, cout, am, B};
+                *y = act_pair(out, (long long)x.L * s * cout, cout, x.L * s, cout, am, B);
                 HIPCHK(h, hipGetLastError());
             }
             return rc;
         }
     }
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(x, 1, 2, PAD_ZERO, 0, 0, nullptr);
-    p.w = h->blob + g.w_off;
-    p.bias = h->blob + g.b_off;
-    p.y = out.raw;
-    p.y_elu = out.elu;
-    p.y_bs = (long long)x.L * g.N;
-    p.y_rs = g.N;
-    p.B = B;
-    p.M = x.L;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    const int rc = run_tap(h, st, p);
-    y->raw = Act{out.raw, (long long)x.L * s * cout, cout, x.L * s, cout, p.amax_out, p.B};
-    y->elu = Act{out.elu, (long long)x.L * s * cout, cout, x.L * s, cout, p.amax_out, p.B};
-    return rc;
+    // the GEMM's row m is [x[m-1] | x[m]] * Wp, g.N = s * cout floats: the consumer reads it as s time steps of cout
+    return tap_layer(h, st, g, {make_seg(x, 1, 2, PAD_ZERO, 0, 0, nullptr)}, B, x.L, TapDst{out, (long long)x.L * g.N, g.N, x.L * s, cout}, Epi{}, y);
 }
 
 
@@ -693,8 +701,7 @@ int launch_rb256_fused(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, con
                            reinterpret_cast<const __bf16*>(h->blob + h->w6_of.at(rb.c3.w_off)), reinterpret_cast<const __bf16*>(h->blob + h->w6_of.at(rb.fused.w_off)));
     }
     HIPCHK(h, hipGetLastError());
-    y->raw = Act{out.raw, b.y_bs, 256, L, 256, b.amax_out, B};
-    y->elu = Act{out.elu, b.y_bs, 256, L, 256, b.amax_out, B};
+    *y = act_pair(out, b.y_bs, 256, L, 256, b.amax_out, B);
     return AC_OK;
 }
 
@@ -707,9 +714,7 @@ int resblock_fwd(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Act
         int rc = launch_rb128_fused6<true>(h, st, rb, x, out, B, PAD_REFLECT, &am);
         if (rc) return rc;
         HIPCHK(h, hipGetLastError());
-        const long long bs = (long long)x.raw.L * 128;
-        y->raw = Act{out.raw, bs, 128, x.raw.L, 128, am, B};
-        y->elu = Act{out.elu, bs, 128, x.raw.L, 128, am, B};
+        *y = act_pair(out, (long long)x.raw.L * 128, 128, x.raw.L, 128, am, B);
         return AC_OK;
     }
     if (rb256_ok(h, rb, x.raw.L) && x.raw.ts == 256 && x.raw.bs == (long long)x.raw.L * 256 && aligned16(x.raw.p) && (out.raw == nullptr || aligned16(out.raw)) &&
@@ -726,9 +731,7 @@ int resblock_fwd(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Act
         else rc = rb.C == 32 ? launch_rb_fused<32, 128, 1>(h, st, rb, x, out, B) : launch_rb_fused<64, 64, 2>(h, st, rb, x, out, B);   // <C, rows per tile, column split>
         if (rc) return rc;
         HIPCHK(h, hipGetLastError());
-        const long long bs = (long long)x.raw.L * rb.C;
-        y->raw = Act{out.raw, bs, rb.C, x.raw.L, rb.C, am, B};
-        y->elu = Act{out.elu, bs, rb.C, x.raw.L, rb.C, am, B};
+        *y = act_pair(out, (long long)x.raw.L * rb.C, rb.C, x.raw.L, rb.C, am, B);
         return AC_OK;
     }
     if (!x.elu.p) return fail(h, AC_ESTATE, "residual block: the two-launch path needs the ELU'd flavour of its input");
@@ -736,24 +739,8 @@ int resblock_fwd(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Act
     int rc = conv_fwd(h, st, rb.c3, x.elu, h->cfg.residual_kernel_size, 1, nullptr, Out{nullptr, hbuf},
                       (long long)x.elu.L * rb.c3.N, rb.c3.N, B, &hv);
     if (rc) return rc;
-    TapGemmParams p{};
-    p.nseg = 2;
-    p.seg[0] = make_seg(hv.elu, 1, 1, PAD_REFLECT, 0, 0, nullptr);
-    p.seg[1] = make_seg(x.raw, 1, 1, PAD_REFLECT, 0, hv.elu.C, nullptr);
-    p.w = h->blob + rb.fused.w_off;
-    p.bias = h->blob + rb.fused.b_off;
-    p.y = out.raw;
-    p.y_elu = out.elu;
-    p.y_bs = (long long)x.raw.L * rb.C;
-    p.y_rs = rb.C;
-    p.B = B;
-    p.M = x.raw.L;
-    p.N = rb.C;
-    p.Ktot = rb.fused.Ktot;
-    rc = run_tap(h, st, p);
-    y->raw = Act{out.raw, p.y_bs, p.y_rs, x.raw.L, rb.C, p.amax_out, p.B};
-    y->elu = Act{out.elu, p.y_bs, p.y_rs, x.raw.L, rb.C, p.amax_out, p.B};
-    return rc;
+    return tap_layer(h, st, rb.fused, {make_seg(hv.elu, 1, 1, PAD_REFLECT, 0, 0, nullptr), make_seg(x.raw, 1, 1, PAD_REFLECT, 0, hv.elu.C, nullptr)}, B, x.raw.L,
+                     TapDst{out, (long long)x.raw.L * rb.C, rb.C}, Epi{}, y);
 }
 
 
@@ -786,8 +773,7 @@ int thin_stem(ac_handle* h, hipStream_t st, const PackedGemm& g, int F, int k, i
         hipLaunchKernelGGL(stem_kernel, dim3(cdiv(T, STEM_TT), B), dim3(256), 0, st, p);
     }
     HIPCHK(h, hipGetLastError());
-    y->raw = Act{out.raw, (long long)T * F, F, T, F, p.amax_out, B};
-    y->elu = Act{out.elu, (long long)T * F, F, T, F, p.amax_out, B};
+    *y = act_pair(out, (long long)T * F, F, T, F, p.amax_out, B);
     return AC_OK;
 }
 
@@ -888,8 +874,7 @@ int enc_front_fwd(ac_handle* h, hipStream_t st, const float* sig, const float* r
     if (h->dev.chain_stream && h->simg.enc_ok) {       // round 6: the sixteen-waves-per-CU form (enc_stream.h, stream_path.hip)
         if (int rc = enc_stream_fwd(h, st, sig, rel_len, B, T, y, dbg_x0, dbg_y1, p.amax_sig, p.amax_out)) return rc;
         HIPCHK(h, hipGetLastError());
-        out->raw = Act{y, (long long)p.M * 64, 64, p.M, 64, p.amax_out, B};
-        out->elu = Act{nullptr, (long long)p.M * 64, 64, p.M, 64, p.amax_out, B};
+        *out = act_pair(Out{y, nullptr}, (long long)p.M * 64, 64, p.M, 64, p.amax_out, B);
         return AC_OK;
     }
     size_t lds = EF_LDS;
@@ -902,8 +887,7 @@ int enc_front_fwd(ac_handle* h, hipStream_t st, const float* sig, const float* r
         hipLaunchKernelGGL(enc_front_kernel, dim3((unsigned)cdiv((int)streams, EF_WAVES)), dim3(64 * EF_WAVES), lds, st, p);
     }
     HIPCHK(h, hipGetLastError());
-    out->raw = Act{y, (long long)p.M * 64, 64, p.M, 64, p.amax_out, B};
-    out->elu = Act{nullptr, (long long)p.M * 64, 64, p.M, 64, p.amax_out, B};
+    *out = act_pair(Out{y, nullptr}, (long long)p.M * 64, 64, p.M, 64, p.amax_out, B);
     return AC_OK;
 }
 
@@ -988,20 +972,8 @@ int lstm_fwd(ac_handle* h, hipStream_t st, const LstmPlan& lp, const Act& x, con
     const bool fuse_env = h->dev.lstm_fuse_in != 0;
     const bool fuse_in = persist && !h->gemm_fp32 && fuse_env && aligned16(x.p) && x.bs % 4 == 0;   // lstm_persist16.h computes W_ih0 * x[t] itself
     // layer-0 input projection for all t: gin[t][b][4D]
-    if (!fuse_in) {
-        TapGemmParams p{};
-        p.nseg = 1;
-        p.seg[0] = make_seg(x, 1, 1, PAD_ZERO, 0, 0, nullptr);
-        p.w = h->blob + lp.ih[0].w_off;
-        p.bias = h->blob + lp.ih[0].b_off;
-        p.y = ws.gin;
-        p.y_bs = 4LL * D;
-        p.y_rs = (long long)B * 4 * D;
-        p.B = B;
-        p.M = T;
-        p.N = 4 * D;
-        p.Ktot = D;
-        int rc = run_tap(h, st, p);
+    if (!fuse_in) {   // (time-major: clip b's row t at (t B + b) 4D)
+        int rc = tap_layer(h, st, lp.ih[0], {make_seg(x, 1, 1, PAD_ZERO, 0, 0, nullptr)}, B, T, TapDst{Out{ws.gin, nullptr}, 4LL * D, (long long)B * 4 * D});
         if (rc) return rc;
     }
     const int nroles = 2 * L - 1, nlaunch = T + 2 * (L - 1);
@@ -1102,8 +1074,7 @@ int lstm_fwd(ac_handle* h, hipStream_t st, const LstmPlan& lp, const Act& x, con
         }
         HIPCHK(h, hipGetLastError());
         const unsigned* am = amax_plus(h, st, x, 1.0f, B);   // |lstm(x) + x| <= 1 + amax(x)
-        y->raw = Act{out.raw, (long long)T * D, D, T, D, am, B};
-        y->elu = Act{out.elu, (long long)T * D, D, T, D, am, B};
+        *y = act_pair(out, (long long)T * D, D, T, D, am, B);
         return AC_OK;
     }
     {
@@ -1163,8 +1134,7 @@ int lstm_fwd(ac_handle* h, hipStream_t st, const LstmPlan& lp, const Act& x, con
     }
     HIPCHK(h, hipGetLastError());
     const unsigned* am = amax_plus(h, st, x, 1.0f, B);
-    y->raw = Act{out.raw, (long long)T * D, D, T, D, am, B};
-    y->elu = Act{out.elu, (long long)T * D, D, T, D, am, B};
+    *y = act_pair(out, (long long)T * D, D, T, D, am, B);
     return AC_OK;
 }
 
@@ -1469,40 +1439,26 @@ int decoder_fwd(ac_handle* h, hipStream_t st, const long long* toks, int B, int 
     return rc;
 }
 
-// y[rows][N] = epi(x[rows][cin-slice] * W^T): a 1-tap GEMM over the merged token matrix.  `x_pitch` is the row
+// y[rows][N] = epi(x[rows][cin-slice] * W^T): a 1-tap GEMM over the merged row matrix.  `x_pitch` is the row
 // pitch of x, `kofs`/`Ktot` select a column block of a wider packed weight.  Rows are chunked so that one
 // launch's operands stay below the 2 GB range of a buffer descriptor.
-int mimi_linear(ac_handle* h, hipStream_t st, const PackedGemm& g, const float* x, long long rows, int cin, int x_pitch, int kofs,
+int linear_rows(ac_handle* h, hipStream_t st, const PackedGemm& g, const float* x, long long rows, int cin, int x_pitch, int kofs,
                 float* y, int y_pitch, const Epi& epi) {
     const long long widest = std::max<long long>(std::max(x_pitch, y_pitch), g.N);
     long long chunk = ((1LL << 31) / 4 - 4096) / widest / 128 * 128;
     if (chunk < 128) return fail(h, AC_EINVAL, "linear layer too wide for the tap-GEMM (%lld)", widest);
     for (long long r0 = 0; r0 < rows; r0 += chunk) {
         const long long n = std::min(chunk, rows - r0);
-        TapGemmParams p{};
-        p.nseg = 1;
         Act xa{x + r0 * x_pitch, 0, x_pitch, (int)n, cin};
         const bool one = r0 == 0 && n == rows;     // row words are chained between launches that cover the whole matrix
         if (one && epi.rowmax_in) { xa.amax = epi.rowmax_in; xa.amax_n = -(int)n; }
-        p.seg[0] = make_seg(xa, 1, 1, PAD_ZERO, 0, kofs, nullptr);
-        if (one && epi.rowmax_out) p.amax_out_rows = reinterpret_cast<unsigned*>(1);   // request; run_tap allocates
-        p.amax_rows = 1;                           // split16.h row mode: every row scales by its own amax
-        p.w = h->blob + g.w_off;
-        p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
-        p.y = y + r0 * y_pitch;
-        p.y_bs = 0;
-        p.y_rs = y_pitch;
-        p.B = 1;
-        p.M = (int)n;
-        p.N = g.N;
-        p.Ktot = g.Ktot;
-        p.scale = epi.scale;
-        p.res = epi.res ? epi.res + r0 * epi.res_rs : nullptr;
-        p.res_bs = 0;
-        p.res_rs = epi.res_rs;
-        p.gelu = epi.gelu;
-        if (int rc = run_tap(h, st, p)) return rc;
-        if (epi.rowmax_out) *epi.rowmax_out = one ? p.amax_out_rows : nullptr;
+        Epi e = epi;
+        e.row_mode = true;                         // split16.h row mode: every row scales by its own amax
+        if (!one) e.rowmax_out = nullptr;
+        if (e.res) e.res += r0 * e.res_rs;
+        e.res_bs = 0;
+        if (int rc = tap_layer(h, st, g, {make_seg(xa, 1, 1, PAD_ZERO, 0, kofs, nullptr)}, 1, (int)n, TapDst{Out{y + r0 * y_pitch, nullptr}, 0, y_pitch}, e)) return rc;
+        if (!one && epi.rowmax_out) *epi.rowmax_out = nullptr;
     }
     return AC_OK;
 }

@@ -20,84 +20,42 @@ namespace acimpl {
 
 static_assert(DAC_D == DAC_CODE_DIM, "core.h mirrors dac.h");
 
-struct SnakeP {
-    const float* a = nullptr;
-    const float* ai = nullptr;
-    int n = 0;
-};
-
-SnakeP dac_snake(const ac_handle* h, size_t a_off, size_t ai_off, int n) { return SnakeP{h->blob + a_off, h->blob + ai_off, n}; }
+// the epilogue terms of a layer whose activated flavour is the Snake with these constants ([n] each, float offsets into the blob)
+Epi dac_snake(const ac_handle* h, size_t a_off, size_t ai_off, int n) {
+    Epi e;
+    e.alpha = h->blob + a_off;
+    e.alpha_inv = h->blob + ai_off;
+    e.alpha_n = n;
+    return e;
+}
 
 // conv with symmetric zero padding `padl` (time steps) and dilation; stride 1 (any k <= 8) or k = 2*stride.
-int dac_conv(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, int k, int s, int dil, int padl, Out out, SnakeP sn, int B,
-             Act2* y, const Epi& epi = Epi{}, int tanh_out = 0) {
-    if (s != 1 && k != 2 * s) return fail(h, AC_EINVAL, "strided conv needs kernel == 2*stride (got k=%d, s=%d)", k, s);
+// `epi`: the Snake of the activated flavour, a residual, the head's tanh
+int dac_conv(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, int k, int s, int dil, int padl, Out out, const Epi& epi, int B, Act2* y) {
+    int J;
+    if (int rc = conv_taps(h, k, s, &J)) return rc;
     const long long span = (long long)x.L + 2LL * padl - (long long)dil * (k - 1) - 1;
     if (span < 0)
         return fail(h, AC_EINVAL, "input too short: %d time steps (+%d padding) for a kernel spanning %d", x.L, 2 * padl, dil * (k - 1) + 1);
     const int M = (int)(span / s) + 1;
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(x, s, s == 1 ? k : 2, PAD_ZERO, 0, 0, nullptr);
-    p.seg[0].pad = padl;
-    p.seg[0].dil = dil;
-    p.w = h->blob + g.w_off;
-    p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
-    p.y = out.raw;
-    p.y_elu = out.elu;
-    p.y_bs = (long long)M * g.N;
-    p.y_rs = g.N;
-    p.B = B;
-    p.M = M;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    p.res = epi.res;
-    p.res_bs = epi.res_bs;
-    p.res_rs = epi.res_rs;
-    p.alpha = sn.a;
-    p.alpha_inv = sn.ai;
-    p.alpha_n = sn.n;
-    p.tanh_out = tanh_out;
-    const int rc = run_tap(h, st, p);
-    if (y) {
-        y->raw = Act{out.raw, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-        y->elu = Act{out.elu, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-    }
-    return rc;
+    TapSeg sg = make_seg(x, s, J, PAD_ZERO, 0, 0, nullptr);
+    sg.pad = padl;
+    sg.dil = dil;
+    return tap_layer(h, st, g, {sg}, B, M, TapDst{out, (long long)M * g.N, g.N}, epi, y);
 }
 
 // transposed conv k = 2s, stride s, padding pp: rows m' = 0..L of s*cout floats, row m' = [x[m'-1] | x[m']] * Wp,
 // holding output samples m'*s - pp .. m'*s - pp + s - 1; only samples in [0, Lout) are stored.
-int dac_convtr(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, int s, int pp, Out out, SnakeP sn, int B, Act2* y) {
+int dac_convtr(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, int s, int pp, Out out, const Epi& snake, int B, Act2* y) {
     const int cout = g.N / s;
     const int Lout = (x.L - 1) * s - 2 * pp + 2 * s;
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(x, 1, 2, PAD_ZERO, 0, 0, nullptr);
-    p.w = h->blob + g.w_off;
-    p.bias = h->blob + g.b_off;
-    p.y = out.raw;
-    p.y_elu = out.elu;
-    p.y_bs = (long long)Lout * cout;
-    p.y_rs = g.N;
-    p.y_off = -(long long)pp * cout;
-    p.y_len = (long long)Lout * cout;
-    p.B = B;
-    p.M = x.L + 1;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    p.alpha = sn.a;
-    p.alpha_inv = sn.ai;
-    p.alpha_n = sn.n;
-    const int rc = run_tap(h, st, p);
-    y->raw = Act{out.raw, p.y_bs, cout, Lout, cout, p.amax_out, p.B};
-    y->elu = Act{out.elu, p.y_bs, cout, Lout, cout, p.amax_out, p.B};
-    return rc;
+    const long long len = (long long)Lout * cout;
+    return tap_layer(h, st, g, {make_seg(x, 1, 2, PAD_ZERO, 0, 0, nullptr)}, B, x.L + 1, TapDst{out, len, g.N, Lout, cout, -(long long)pp * cout, len}, snake, y);
 }
 
 // the 96-channel ResidualUnit as ONE kernel (dac_unit6.h); returns false when the shape, the alignment or the arithmetic mode
 // asks for the two tap-GEMM launches (then nothing was launched)
-bool dac_unit_fused(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int C, const Act2& x, Out out, SnakeP next, int B, Act2* y, int* rc_out) {
+bool dac_unit_fused(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int C, const Act2& x, Out out, Epi next, int B, Act2* y, int* rc_out) {
     *rc_out = AC_OK;
     // (96 channels only: measured per unit, 32 clips -- 14.5 -> 13.9 ms; the 64-channel units LOSE, 6.9 -> 8.7 ms: their two-launch path runs
     //  64 x 32 wave tiles at three workgroups per CU, the wave-local second product needs 32 x 64 ones; profiles/r4_variants.md.
@@ -105,7 +63,7 @@ bool dac_unit_fused(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int 
     //  The test hook does not change the route: it wants each unit's OUTPUT only, dac_res_unit then asks for the raw flavour of
     //  every unit (want_raw) and the kernel's epilogue writes it -- so the kernel the hook sees is the one that ships.)
     if (h->gemm_fp32 || h->dev.dac_unit == 0 || h->dev.tap_dil == 0 || h->dev.tap_epi_staged != 0 || C != 96 || ru.c7.N != C || ru.c1.N != C || ru.c1.Ktot != C || ru.c7.Ktot != 7 * C) return false;
-    if (!ru.c7.has_bias || !ru.c1.has_bias || !out.elu || !next.a || next.n < C) return false;
+    if (!ru.c7.has_bias || !ru.c1.has_bias || !out.elu || !next.alpha || next.alpha_n < C) return false;
     auto w1 = h->w6_of.find(ru.c7.w_off), w2 = h->w6_of.find(ru.c1.w_off);
     auto i1 = h->winv_of.find(ru.c7.w_off), i2 = h->winv_of.find(ru.c1.w_off);
     if (w1 == h->w6_of.end() || w2 == h->w6_of.end() || i1 == h->winv_of.end() || i2 == h->winv_of.end()) return false;
@@ -137,9 +95,9 @@ bool dac_unit_fused(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int 
     p.res = xr.p;
     p.res_bs = xr.bs;
     p.res_rs = xr.ts;
-    p.alpha = next.a;
-    p.alpha_inv = next.ai;
-    p.alpha_n = next.n;
+    p.alpha = next.alpha;
+    p.alpha_inv = next.alpha_inv;
+    p.alpha_n = next.alpha_n;
     p.amax_out = amax_new(h);
     if (!p.amax_out) { *rc_out = fail(h, AC_ESTATE, "out of amax slots (split16.h)"); return true; }
     p.epi_direct = 1;
@@ -166,13 +124,12 @@ bool dac_unit_fused(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int 
     if (dil == 1) DAC_UNIT_LAUNCH(3, 7, "dac_unit6_kernel<3>"); else DAC_UNIT_LAUNCH(3, T6_DIL_HALO, "dac_unit6_kernel<3, dil>");
 #undef DAC_UNIT_LAUNCH
     if (hipGetLastError() != hipSuccess) { *rc_out = fail(h, AC_ESTATE, "dac_unit6 launch failed"); return true; }
-    y->raw = Act{out.raw, p.y_bs, C, L, C, p.amax_out, B};
-    y->elu = Act{out.elu, p.y_bs, C, L, C, p.amax_out, B};
+    *y = act_pair(out, p.y_bs, C, L, C, p.amax_out, B);
     return true;
 }
 
 // one ResidualUnit; `next`: Snake of whatever consumes the unit's output; `want_raw`: the next layer is another unit
-int dac_res_unit(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int C, const Act2& x, WsPtrs& ws, SnakeP next, bool want_raw, int B,
+int dac_res_unit(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int C, const Act2& x, WsPtrs& ws, Epi next, bool want_raw, int B,
                  Act2* y) {
     {
         Out o{want_raw ? ws.take() : nullptr, ws.take()};
@@ -185,11 +142,11 @@ int dac_res_unit(ac_handle* h, hipStream_t st, const DacResUnitPlan& ru, int C, 
     Act2 hv;
     int rc = dac_conv(h, st, ru.c7, x.elu, 7, 1, ru.dil, 3 * ru.dil, Out{nullptr, hb}, dac_snake(h, ru.a2, ru.a2i, C), B, &hv);
     if (rc) return rc;
-    Epi e;
+    Epi e = next;
     e.res = x.raw.p;
     e.res_bs = x.raw.bs;
     e.res_rs = x.raw.ts;
-    rc = dac_conv(h, st, ru.c1, hv.elu, 1, 1, 1, 0, Out{want_raw ? ws.take() : nullptr, ws.take()}, next, B, y, e);
+    rc = dac_conv(h, st, ru.c1, hv.elu, 1, 1, 1, 0, Out{want_raw ? ws.take() : nullptr, ws.take()}, e, B, y);
     ws.give(hb);
     return rc;
 }
@@ -268,12 +225,12 @@ int dac_encoder_fwd(ac_handle* h, hipStream_t st, const float* sig, int B, int T
     const bool dbg = h->dbg != nullptr;
     const int F = c.encoder_hidden_size;
     const DacBlockPlan& b0 = m.enc[0];
-    const SnakeP s0 = dac_snake(h, b0.ru[0].a1, b0.ru[0].a1i, F);
+    const Epi s0 = dac_snake(h, b0.ru[0].a1, b0.ru[0].a1i, F);
     Act xin{sig, (long long)T, 1, T, 1};
     Act2 x, y;
     int rc;
     if (F % 4 == 0 && F <= 64)
-        rc = thin_stem(h, st, m.enc_stem, F, 7, PAD_ZERO, sig, nullptr, B, T, Out{ws.take(), ws.take()}, &x, 3, s0.a, s0.ai);
+        rc = thin_stem(h, st, m.enc_stem, F, 7, PAD_ZERO, sig, nullptr, B, T, Out{ws.take(), ws.take()}, &x, 3, s0.alpha, s0.alpha_inv);
     else
         rc = dac_conv(h, st, m.enc_stem, xin, 7, 1, 1, 3, Out{ws.take(), ws.take()}, s0, B, &x);
     if (rc) return rc;
@@ -284,7 +241,7 @@ int dac_encoder_fwd(ac_handle* h, hipStream_t st, const float* sig, int B, int T
         const int nu = (int)blk.ru.size();
         for (int u = 0; u < nu; ++u) {
             const bool last_u = u == nu - 1;
-            const SnakeP next = last_u ? dac_snake(h, blk.a, blk.ai, blk.C) : dac_snake(h, blk.ru[u + 1].a1, blk.ru[u + 1].a1i, blk.C);
+            const Epi next = last_u ? dac_snake(h, blk.a, blk.ai, blk.C) : dac_snake(h, blk.ru[u + 1].a1, blk.ru[u + 1].a1i, blk.C);
             rc = dac_res_unit(h, st, blk.ru[u], blk.C, x, ws, next, !last_u || dbg, B, &y);
             if (rc) return rc;
             ws.give(x);
@@ -294,7 +251,7 @@ int dac_encoder_fwd(ac_handle* h, hipStream_t st, const float* sig, int B, int T
         }
         const bool last = i == nb - 1;
         const int s = blk.stride, cout = blk.conv.N;
-        const SnakeP next = last ? dac_snake(h, m.enc_a, m.enc_ai, cout) : dac_snake(h, m.enc[i + 1].ru[0].a1, m.enc[i + 1].ru[0].a1i, cout);
+        const Epi next = last ? dac_snake(h, m.enc_a, m.enc_ai, cout) : dac_snake(h, m.enc[i + 1].ru[0].a1, m.enc[i + 1].ru[0].a1i, cout);
         rc = dac_conv(h, st, blk.conv, x.elu, 2 * s, s, 1, dac_ceil_half(s), Out{(!last || dbg) ? ws.take() : nullptr, ws.take()}, next, B, &y);
         if (rc) return rc;
         ws.give(x);
@@ -302,7 +259,7 @@ int dac_encoder_fwd(ac_handle* h, hipStream_t st, const float* sig, int B, int T
         if (!last || dbg) capture(h, st, x.raw, B);
         if (last && dbg) { ws.give(x.raw.p); x.raw.p = nullptr; }
     }
-    rc = dac_conv(h, st, m.enc_final, x.elu, 3, 1, 1, 1, Out{z, nullptr}, SnakeP{}, B, &y);
+    rc = dac_conv(h, st, m.enc_final, x.elu, 3, 1, 1, 1, Out{z, nullptr}, Epi{}, B, &y);
     ws.give(x);
     if (rc) return rc;
     capture(h, st, y.raw, B);
@@ -333,7 +290,7 @@ int dac_decoder_fwd(ac_handle* h, hipStream_t st, const float* zq, int B, int N,
         const int nu = (int)blk.ru.size();
         for (int u = 0; u < nu; ++u) {
             const bool last_u = u == nu - 1;
-            SnakeP next;
+            Epi next;
             if (!last_u) next = dac_snake(h, blk.ru[u + 1].a1, blk.ru[u + 1].a1i, blk.C);
             else if (i + 1 < nb) next = dac_snake(h, m.dec[i + 1].a, m.dec[i + 1].ai, blk.C);
             else next = dac_snake(h, m.dec_a, m.dec_ai, blk.C);
@@ -348,8 +305,11 @@ int dac_decoder_fwd(ac_handle* h, hipStream_t st, const float* zq, int B, int N,
     const int F = m.dec_head.Ktot / 7;
     if (F % 4 == 0 && F <= 128 && x.elu.ts == F)
         rc = thin_head(h, st, m.dec_head, F, 7, PAD_ZERO, x.elu, B, sig, 3, 1);
-    else
-        rc = dac_conv(h, st, m.dec_head, x.elu, 7, 1, 1, 3, Out{sig, nullptr}, SnakeP{}, B, nullptr, Epi{}, 1);
+    else {
+        Epi eh;
+        eh.tanh_out = 1;
+        rc = dac_conv(h, st, m.dec_head, x.elu, 7, 1, 1, 3, Out{sig, nullptr}, eh, B, nullptr);
+    }
     ws.give(x);
     return rc;
 }
@@ -522,7 +482,7 @@ int dac_finalize(ac_handle* h, Packer& pk) {
 int dac_latent_proj(ac_handle* h, hipStream_t st, const float* z, int N, int nb, float* zlat) {
     const int H = h->dac.H;
     Act za{z, (long long)N * H, H, N, H};
-    return dac_conv(h, st, h->dac.in_proj0, za, 1, 1, 1, 0, Out{zlat, nullptr}, SnakeP{}, nb, nullptr);
+    return dac_conv(h, st, h->dac.in_proj0, za, 1, 1, 1, 0, Out{zlat, nullptr}, Epi{}, nb, nullptr);
 }
 
 }  // namespace acimpl

@@ -107,19 +107,9 @@ static int estream_lstm_proj(ac_handle* h, hipStream_t st, const PackedGemm& g, 
         HIPCHK(h, hipGetLastError());
         return AC_OK;
     }
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(x, 1, 1, PAD_ZERO, 0, 0, nullptr);
-    p.w = h->blob + g.w_off;
-    p.bias = nullptr;
-    p.y = gin;
-    p.y_bs = (long long)F * 4 * D;
-    p.y_rs = 4LL * D;
-    p.B = B;
-    p.M = F;
-    p.N = 4 * D;
-    p.Ktot = D;
-    return run_tap(h, st, p);
+    Epi e;
+    e.no_bias = true;
+    return tap_layer(h, st, g, {make_seg(x, 1, 1, PAD_ZERO, 0, 0, nullptr)}, B, F, TapDst{Out{gin, nullptr}, (long long)F * 4 * D, 4LL * D}, e);
 }
 
 // x [B][F][D] -> ELU(lstm(x) + x) [B][F][D] at `yelu`, from the state's h / c, which it leaves at the push's last step
@@ -183,8 +173,7 @@ static int estream_lstm(ac_handle* h, hipStream_t st, const LstmPlan& lp, const 
         HIPCHK(h, hipGetLastError());
     }
     const unsigned* am = amax_plus(h, st, x, 1.0f, B);   // |lstm(x) + x| <= 1 + amax(x)
-    y->raw = Act{nullptr, FD, D, F, D, am, B};
-    y->elu = Act{yelu, FD, D, F, D, am, B};
+    *y = act_pair(Out{nullptr, yelu}, FD, D, F, D, am, B);
     return AC_OK;
 }
 
@@ -200,24 +189,10 @@ static int estream_resblock(ac_handle* h, hipStream_t st, char* state, const ESt
     if ((rc = mstream_conv(h, st, rb.c3, staged_act(stg, B, L + Ls.conv_P[l], ch), h->cfg.residual_kernel_size, 1, L, Out{nullptr, hb}, B, &hv))) return rc;
     ws.give(stg);
     float* ye = ws.take();
-    TapGemmParams p{};
-    p.nseg = 2;
-    p.seg[0] = make_seg(hv.elu, 1, 1, PAD_ZERO, 0, 0, nullptr);
-    p.seg[1] = make_seg(x.raw, 1, 1, PAD_ZERO, 0, hv.elu.C, nullptr);
-    p.w = h->blob + rb.fused.w_off;
-    p.bias = h->blob + rb.fused.b_off;
-    p.y = nullptr;
-    p.y_elu = ye;
-    p.y_bs = (long long)L * ch;
-    p.y_rs = ch;
-    p.B = B;
-    p.M = L;
-    p.N = ch;
-    p.Ktot = rb.fused.Ktot;
-    if ((rc = run_tap(h, st, p))) return rc;
+    if ((rc = tap_layer(h, st, rb.fused, {make_seg(hv.elu, 1, 1, PAD_ZERO, 0, 0, nullptr), make_seg(x.raw, 1, 1, PAD_ZERO, 0, hv.elu.C, nullptr)}, B, L,
+                        TapDst{Out{nullptr, ye}, (long long)L * ch, ch}, Epi{}, y)))
+        return rc;
     ws.give(hb);
-    y->raw = Act{nullptr, p.y_bs, p.y_rs, L, ch, p.amax_out, p.B};
-    y->elu = Act{ye, p.y_bs, p.y_rs, L, ch, p.amax_out, p.B};
     return AC_OK;
 }
 

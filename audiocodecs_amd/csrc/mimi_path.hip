@@ -21,31 +21,9 @@ int mimi_conv(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, i
               const Epi& epi = Epi{}) {
     const int M = cdiv(x.L, s);
     const int extra = M * s - x.L;
-    if (s != 1 && k != 2 * s) return fail(h, AC_EINVAL, "strided conv needs kernel == 2*stride (got k=%d, s=%d)", k, s);
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(x, s, s == 1 ? k : 2, pad, extra, 0, nullptr);
-    p.w = h->blob + g.w_off;
-    p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
-    p.y = out.raw;
-    p.y_elu = out.elu;
-    p.y_bs = (long long)M * g.N;
-    p.y_rs = g.N;
-    p.B = B;
-    p.M = M;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    p.scale = epi.scale;
-    p.res = epi.res;
-    p.res_bs = epi.res_bs;
-    p.res_rs = epi.res_rs;
-    p.gelu = epi.gelu;
-    const int rc = run_tap(h, st, p);
-    if (y) {
-        y->raw = Act{out.raw, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-        y->elu = Act{out.elu, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-    }
-    return rc;
+    int J;
+    if (int rc = conv_taps(h, k, s, &J)) return rc;
+    return tap_layer(h, st, g, {make_seg(x, s, J, pad, extra, 0, nullptr)}, B, M, TapDst{out, (long long)M * g.N, g.N}, epi, y);
 }
 
 
@@ -59,8 +37,7 @@ int mimi_resblock(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Ac
         int rc = rb128_identity_fwd(h, st, rb, x, out, B, &am);
         if (rc) return rc;
         HIPCHK(h, hipGetLastError());
-        y->raw = Act{out.raw, bs, rb.C, x.raw.L, rb.C, am, B};
-        y->elu = Act{out.elu, bs, rb.C, x.raw.L, rb.C, am, B};
+        *y = act_pair(out, bs, rb.C, x.raw.L, rb.C, am, B);
         return AC_OK;
     }
     if (rb.C == 64 && c.residual_kernel_size == 3 && c.compress == 2 && x.raw.ts == rb.C && x.raw.bs == bs && aligned16(x.raw.p) &&
@@ -69,8 +46,7 @@ int mimi_resblock(ac_handle* h, hipStream_t st, const ResBlockPlan& rb, const Ac
         int rc = rb64_identity_fwd(h, st, rb, x, out, B, &am);
         if (rc) return rc;
         HIPCHK(h, hipGetLastError());
-        y->raw = Act{out.raw, bs, rb.C, x.raw.L, rb.C, am, B};
-        y->elu = Act{out.elu, bs, rb.C, x.raw.L, rb.C, am, B};
+        *y = act_pair(out, bs, rb.C, x.raw.L, rb.C, am, B);
         return AC_OK;
     }
     Act2 hv;
@@ -153,26 +129,26 @@ int transformer_fwd(ac_handle* h, hipStream_t st, const std::vector<MimiTfLayer>
         if (rc) return rc;
         Epi eq;
         eq.rowmax_in = ln_rows;
-        if ((rc = mimi_linear(h, st, L.qkv, s.ln, rows, H, H, 0, s.qkv, 3 * A, eq))) return rc;
+        if ((rc = linear_rows(h, st, L.qkv, s.ln, rows, H, H, 0, s.qkv, 3 * A, eq))) return rc;
         if ((rc = attention_fwd(h, st, s.qkv, s.att, B, T))) return rc;
         Epi ea;
         ea.scale = h->blob + L.sc_a;
         ea.res = x;
         ea.res_rs = H;
-        if ((rc = mimi_linear(h, st, L.o, s.att, rows, A, A, 0, x, H, ea))) return rc;
+        if ((rc = linear_rows(h, st, L.o, s.att, rows, A, A, 0, x, H, ea))) return rc;
         if ((rc = layernorm_fwd(h, st, x, L.ln2_w, L.ln2_b, s.ln, rows, H, c.norm_eps, &ln_rows))) return rc;
         Epi eg;
         eg.gelu = 1;
         eg.rowmax_in = ln_rows;
         const unsigned* hid_rows = nullptr;      // split16.h row mode: fc1's epilogue leaves the row amax of its output for fc2
         eg.rowmax_out = &hid_rows;
-        if ((rc = mimi_linear(h, st, L.fc1, s.ln, rows, H, H, 0, s.hid, I, eg))) return rc;
+        if ((rc = linear_rows(h, st, L.fc1, s.ln, rows, H, H, 0, s.hid, I, eg))) return rc;
         Epi em;
         em.rowmax_in = hid_rows;
         em.scale = h->blob + L.sc_m;
         em.res = x;
         em.res_rs = H;
-        if ((rc = mimi_linear(h, st, L.fc2, s.hid, rows, I, I, 0, x, H, em))) return rc;
+        if ((rc = linear_rows(h, st, L.fc2, s.hid, rows, I, I, 0, x, H, em))) return rc;
         capture(h, st, Act{x, (long long)T * H, H, T, H}, B);
     }
     return AC_OK;
@@ -233,21 +209,10 @@ int mimi_rvq_decode(ac_handle* h, hipStream_t st, const long long* toks, int F, 
         HIPCHK(h, hipGetLastError());
     }
     // one GEMM over the K-concatenation [q_s | q_a] (only the semantic columns when K <= num_semantic_quantizers)
-    TapGemmParams p{};
-    p.nseg = 1;
     Act qa{qsum, 0, 2 * Dq, F, nparts * Dq};
-    p.seg[0] = make_seg(qa, 1, 1, PAD_ZERO, 0, 0, nullptr);
-    p.w = h->blob + h->mimi.out_proj.w_off;
-    p.bias = nullptr;
-    p.y = qfeats;
-    p.y_bs = 0;
-    p.y_rs = H;
-    p.B = 1;
-    p.M = F;
-    p.N = H;
-    p.Ktot = 2 * Dq;
-    p.amax_rows = 1;                               // split16.h row mode: a merged row matrix, every row scales by its own amax
-    return run_tap(h, st, p);
+    Epi e;
+    e.row_mode = true;                             // split16.h row mode: a merged row matrix, every row scales by its own amax
+    return tap_layer(h, st, h->mimi.out_proj, {make_seg(qa, 1, 1, PAD_ZERO, 0, 0, nullptr)}, 1, F, TapDst{Out{qfeats, nullptr}, 0, H}, e);   // (packed without a bias)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -320,8 +285,7 @@ int mimi_encoder_fwd(ac_handle* h, hipStream_t st, const float* sig, int B, int 
         rc = launch_rb_stream6m(h, st, m.enc_rb[0], nullptr, sig, B, T, o, nullptr, 0, am_sig, am_out);
         if (rc) return rc;
         HIPCHK(h, hipGetLastError());
-        x.raw = Act{nullptr, (long long)T * 64, 64, T, 64, am_out, B};
-        x.elu = Act{o.elu, (long long)T * 64, 64, T, 64, am_out, B};
+        x = act_pair(o, (long long)T * 64, 64, T, 64, am_out, B);
         first_block = 1;
     } else
     if (F % 4 == 0 && F <= 64 && c.kernel_size <= THIN_MAXK)

@@ -129,9 +129,9 @@ static void mstream_linear_launch(hipStream_t st, const MStreamLinearParams& p) 
     else hipLaunchKernelGGL((mstream_linear_kernel<RB, 1>), grid, dim3(64), 0, st, p);
 }
 
-// y[rows][N] = epi(x[rows][K] W^T) as mimi_linear computes it, on the plain fp32 matrix; shapes the kernel does not take go to mimi_linear
+// y[rows][N] = epi(x[rows][K] W^T) as linear_rows computes it, on the plain fp32 matrix; shapes the kernel does not take go to linear_rows
 static int mstream_linear(ac_handle* h, hipStream_t st, const PackedGemm& g, const float* x, long long rows, int K, float* y, int y_pitch, const Epi& epi, bool skinny) {
-    if (!skinny || rows > 65535LL * 8 || !mstream_skinny_ok(g, x, K, y, y_pitch, K)) return mimi_linear(h, st, g, x, rows, K, K, 0, y, y_pitch, epi);
+    if (!skinny || rows > 65535LL * 8 || !mstream_skinny_ok(g, x, K, y, y_pitch, K)) return linear_rows(h, st, g, x, rows, K, K, 0, y, y_pitch, epi);
     MStreamLinearParams p{};
     p.x = x;
     p.w = h->blob + g.w_off;
@@ -446,7 +446,7 @@ static int mstream_encode(ac_handle* h, void* state_dev, size_t state_bytes, int
     rc = mstream_encoder(h, st, static_cast<char*>(state_dev), Ls, slots_dev, sig_dev, n, F, feats, p, w.act_floats);
     if (rc) return rc;
     float* proj = p.take();
-    rc = mimi_linear(h, st, h->mimi.in_proj, feats, (long long)n * F, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
+    rc = linear_rows(h, st, h->mimi.in_proj, feats, (long long)n * F, c.hidden_size, c.hidden_size, 0, proj, 2 * c.codebook_dim);
     if (rc) return rc;
     return mimi_rvq_encode(h, st, proj, n * F, K, reinterpret_cast<long long*>(toks_dev));
 }

@@ -77,23 +77,14 @@ static SpkWs spk_plan_ws(const ac_handle* h, int B, long long L) {
 
 // one conv / TDNN layer through the tap-GEMM: x viewed as rows of s time steps, J taps `dil` rows apart, no padding, M output rows
 static int spk_conv(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, int s, int J, int dil, int M, float* y, int gelu, int B, Act* out) {
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(x, s, J, PAD_ZERO, 0, 0, nullptr, 0, 0);
-    p.seg[0].dil = dil;
-    p.w = h->blob + g.w_off;
-    p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
-    p.y = y;
-    p.y_bs = (long long)M * g.N;
-    p.y_rs = g.N;
-    p.B = B;
-    p.M = M;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    p.gelu = gelu;
-    const int rc = run_tap(h, st, p);
-    *out = Act{y, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-    return rc;
+    TapSeg sg = make_seg(x, s, J, PAD_ZERO, 0, 0, nullptr, 0, 0);
+    sg.dil = dil;
+    Epi e;
+    e.gelu = gelu;
+    Act2 o;
+    if (int rc = tap_layer(h, st, g, {sg}, B, M, TapDst{Out{y, nullptr}, (long long)M * g.N, g.N}, e, &o)) return rc;
+    *out = o.raw;
+    return AC_OK;
 }
 
 static unsigned grid1d(long long n, int per) { return (unsigned)std::max<long long>(1, std::min<long long>((n + per - 1) / per, 65535LL * 16)); }
@@ -158,7 +149,7 @@ static int spk_chunk_fwd(ac_handle* h, hipStream_t st, const float* sig, const i
     {
         Epi e;
         e.rowmax_in = ln_rows;
-        if ((rc = mimi_linear(h, st, m.fp, feat, rows, C, C, 0, x, H, e))) return rc;
+        if ((rc = linear_rows(h, st, m.fp, feat, rows, C, C, 0, x, H, e))) return rc;
     }
     if (valid) {
         ProfScope ps(h, st, "spk_mask_rows_kernel", 0.0, 4.0 * rows * H);
@@ -199,7 +190,7 @@ static int spk_chunk_fwd(ac_handle* h, hipStream_t st, const float* sig, const i
                                h->blob + Ly.gate_c, gate, nb, T, heads);
             HIPCHK(h, hipGetLastError());
         }
-        if ((rc = mimi_linear(h, st, Ly.qkv, x, rows, H, H, 0, qkv, 3 * H))) return rc;
+        if ((rc = linear_rows(h, st, Ly.qkv, x, rows, H, H, 0, qkv, 3 * H))) return rc;
         {
             WavlmAttnParams p{qkv, att, gate, h->blob + m.bias_tab, lens, nb, T, H, m.R, 0.125f};
             const size_t lds = WavlmAttnCfg::lds_bytes(T);
@@ -211,26 +202,26 @@ static int spk_chunk_fwd(ac_handle* h, hipStream_t st, const float* sig, const i
         Epi ea;
         ea.res = x;
         ea.res_rs = H;
-        if ((rc = mimi_linear(h, st, Ly.o, att, rows, H, H, 0, x, H, ea))) return rc;
+        if ((rc = linear_rows(h, st, Ly.o, att, rows, H, H, 0, x, H, ea))) return rc;
         if ((rc = layernorm_fwd(h, st, x, Ly.ln1_w, Ly.ln1_b, x, rows, H, c.layer_norm_eps, &ln_rows))) return rc;
         Epi eg;
         eg.gelu = 1;
         eg.rowmax_in = ln_rows;
         const unsigned* hid_rows = nullptr;
         eg.rowmax_out = &hid_rows;
-        if ((rc = mimi_linear(h, st, Ly.fc1, x, rows, H, H, 0, hid, I, eg))) return rc;
+        if ((rc = linear_rows(h, st, Ly.fc1, x, rows, H, H, 0, hid, I, eg))) return rc;
         Epi em;
         em.rowmax_in = hid_rows;
         em.res = x;
         em.res_rs = H;
-        if ((rc = mimi_linear(h, st, Ly.fc2, hid, rows, I, I, 0, x, H, em))) return rc;
+        if ((rc = linear_rows(h, st, Ly.fc2, hid, rows, I, I, 0, x, H, em))) return rc;
         if ((rc = layernorm_fwd(h, st, x, Ly.ln2_w, Ly.ln2_b, x, rows, H, c.layer_norm_eps, nullptr))) return rc;
     }
     if ((rc = state(nl))) return rc;
     // ---- x-vector head: projector, TDNN layers (dilated convs without padding + ReLU), statistic pooling, feature_extractor
     float* t0 = F(w.t0);
     float* t1 = F(w.t1);
-    if ((rc = mimi_linear(h, st, m.proj, acc, rows, H, H, 0, t0, m.proj.N))) return rc;
+    if ((rc = linear_rows(h, st, m.proj, acc, rows, H, H, 0, t0, m.proj.N))) return rc;
     Act ta{t0, (long long)T * m.proj.N, m.proj.N, T, m.proj.N};
     int M = T;
     for (int i = 0; i < c.num_tdnn_layers; ++i) {
@@ -251,7 +242,7 @@ static int spk_chunk_fwd(ac_handle* h, hipStream_t st, const float* sig, const i
         HIPCHK(h, hipGetLastError());
     }
     if (sg.pooled) HIPCHK(h, hipMemcpyAsync(sg.pooled, pooled, (size_t)nb * 2 * last * 4, hipMemcpyDeviceToDevice, st));
-    return mimi_linear(h, st, m.fe, pooled, nb, 2 * last, 2 * last, 0, emb, m.fe.N);
+    return linear_rows(h, st, m.fe, pooled, nb, 2 * last, 2 * last, 0, emb, m.fe.N);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -72,29 +72,7 @@ static int stream_stage(ac_handle* h, hipStream_t st, float* cache, const int* f
 // a causal conv on a staged input: M outputs, output m reads staged rows [m*s, m*s + k) (no padding left)
 static int mstream_conv(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& xs, int k, int s, int M, Out out, int B, Act2* y,
                         const Epi& epi = Epi{}) {
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(xs, s, s == 1 ? k : 2, PAD_ZERO, 0, 0, nullptr, 0, 0);
-    p.w = h->blob + g.w_off;
-    p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
-    p.y = out.raw;
-    p.y_elu = out.elu;
-    p.y_bs = (long long)M * g.N;
-    p.y_rs = g.N;
-    p.B = B;
-    p.M = M;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    p.scale = epi.scale;
-    p.res = epi.res;
-    p.res_bs = epi.res_bs;
-    p.res_rs = epi.res_rs;
-    const int rc = run_tap(h, st, p);
-    if (y) {
-        y->raw = Act{out.raw, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-        y->elu = Act{out.elu, p.y_bs, p.y_rs, M, g.N, p.amax_out, p.B};
-    }
-    return rc;
+    return tap_layer(h, st, g, {make_seg(xs, s, s == 1 ? k : 2, PAD_ZERO, 0, 0, nullptr, 0, 0)}, B, M, TapDst{out, (long long)M * g.N, g.N}, epi, y);
 }
 
 }  // namespace acimpl

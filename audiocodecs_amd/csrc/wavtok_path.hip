@@ -192,24 +192,7 @@ int wavtok_finalize(ac_handle* h, Packer& pk) {
 // ---------------------------------------------------------------------------------------------
 // conv over each clip's frames with zero padding (left, right) -- nn.Conv1d(padding=p); out contiguous [B][N][g.N]
 int wt_conv(ac_handle* h, hipStream_t st, const PackedGemm& g, const Act& x, int k, int left, int right, float* y, int B, const Epi& epi = Epi{}) {
-    TapGemmParams p{};
-    p.nseg = 1;
-    p.seg[0] = make_seg(x, 1, k, PAD_ZERO, 0, 0, nullptr, left, right);
-    p.w = h->blob + g.w_off;
-    p.bias = g.has_bias ? h->blob + g.b_off : nullptr;
-    p.y = y;
-    p.y_bs = (long long)x.L * g.N;
-    p.y_rs = g.N;
-    p.B = B;
-    p.M = x.L;
-    p.N = g.N;
-    p.Ktot = g.Ktot;
-    p.scale = epi.scale;
-    p.res = epi.res;
-    p.res_bs = epi.res_bs;
-    p.res_rs = epi.res_rs;
-    p.gelu = epi.gelu;
-    return run_tap(h, st, p);
+    return tap_layer(h, st, g, {make_seg(x, 1, k, PAD_ZERO, 0, 0, nullptr, left, right)}, B, x.L, TapDst{Out{y, nullptr}, (long long)x.L * g.N, g.N}, epi);
 }
 
 int wt_groupnorm(ac_handle* h, hipStream_t st, const float* x, size_t w_off, size_t b_off, float* stats, float* y, int B, int N, int swish) {
@@ -255,7 +238,7 @@ int wt_pos_net(ac_handle* h, hipStream_t st, float* x, float* t, float* u, float
     if ((rc = resnet(m.rn[0])) || (rc = resnet(m.rn[1]))) return rc;
     {   // AttnBlock
         if ((rc = wt_groupnorm(h, st, x, m.an_w, m.an_b, stats, t, B, N, 0))) return rc;
-        if ((rc = mimi_linear(h, st, m.qkv, t, rows, C, C, 0, u, 3 * C))) return rc;
+        if ((rc = linear_rows(h, st, m.qkv, t, rows, C, C, 0, u, 3 * C))) return rc;
         Attn1Params ap{u, v, B, N, C, 1.0f / std::sqrt((float)C)};
         {
             ProfScope ps(h, st, "attn1_kernel", 4.0 * B * (double)N * N * C, 16.0 * B * N * C);
@@ -268,7 +251,7 @@ int wt_pos_net(ac_handle* h, hipStream_t st, float* x, float* t, float* u, float
         Epi ep;
         ep.res = x;
         ep.res_rs = C;
-        if ((rc = mimi_linear(h, st, m.proj, v, rows, C, C, 0, x, C, ep))) return rc;
+        if ((rc = linear_rows(h, st, m.proj, v, rows, C, C, 0, x, C, ep))) return rc;
         capture(h, st, xa, B);
     }
     if ((rc = resnet(m.rn[2])) || (rc = resnet(m.rn[3]))) return rc;
@@ -313,13 +296,13 @@ int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, 
         eg.rowmax_in = t_rows;
         const unsigned* u_rows = nullptr;        // split16.h row mode: p1's epilogue leaves the row amax of its output for p2
         eg.rowmax_out = &u_rows;
-        if ((rc = mimi_linear(h, st, L.p1, t, rows, C, C, 0, u, I, eg))) return rc;
+        if ((rc = linear_rows(h, st, L.p1, t, rows, C, C, 0, u, I, eg))) return rc;
         Epi em;
         em.rowmax_in = u_rows;
         em.scale = h->blob + L.gamma;
         em.res = x;
         em.res_rs = C;
-        if ((rc = mimi_linear(h, st, L.p2, u, rows, I, I, 0, x, C, em))) return rc;
+        if ((rc = linear_rows(h, st, L.p2, u, rows, I, I, 0, x, C, em))) return rc;
         capture(h, st, xa, B);
     }
     const unsigned* fl_rows = nullptr;
@@ -328,7 +311,7 @@ int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, 
     // ---- head
     Epi eh;
     eh.rowmax_in = fl_rows;
-    if ((rc = mimi_linear(h, st, m.head, t, rows, C, C, 0, u, m.npad, eh))) return rc;
+    if ((rc = linear_rows(h, st, m.head, t, rows, C, C, 0, u, m.npad, eh))) return rc;
     {
         PolarParams p{u, rows, m.npad, m.bins};
         const long long total = rows * (m.npad / 2);
@@ -337,8 +320,6 @@ int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, 
         HIPCHK(h, hipGetLastError());
     }
     {
-        TapGemmParams p{};
-        p.nseg = 1;
         Act ua{u, (long long)N * m.npad, m.npad, N, m.npad};
         if (unsigned* slot = amax_new(h)) {      // split16.h: polar_kernel clamps the magnitude at 100 -- a bound instead of a pass
             const float bound = 100.0f;
@@ -350,20 +331,12 @@ int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, 
                 ua.amax_n = B;
             }
         }
-        p.seg[0] = make_seg(ua, 1, m.taps, PAD_ZERO, 0, 0, nullptr);
-        p.w = h->blob + m.istft.w_off;
-        p.bias = nullptr;
-        p.y = sig;
-        p.y_bs = (long long)N * hop;
-        p.y_rs = hop;
-        p.B = B;
-        p.M = N + m.taps - 1;
-        p.N = m.istft.N;
-        p.n_valid = hop;
-        p.Ktot = m.istft.Ktot;
-        p.y_off = -(long long)(c.n_fft - hop) / 2;
-        p.y_len = (long long)N * hop;
-        if ((rc = run_tap(h, st, p))) return rc;
+        // overlap-add as a conv of `taps` frames: rows of hop samples (the matrix is padded to istft.N columns, packed without a bias),
+        // shifted by the (n_fft - hop) / 2 samples the reference trims, stored inside the clip only
+        const long long len = (long long)N * hop;
+        if ((rc = tap_layer(h, st, m.istft, {make_seg(ua, 1, m.taps, PAD_ZERO, 0, 0, nullptr)}, B, N + m.taps - 1,
+                            TapDst{Out{sig, nullptr}, len, hop, 0, 0, -(long long)(c.n_fft - hop) / 2, len, hop})))
+            return rc;
     }
     {
         EnvParams p{sig, h->blob + m.w2, B, N, hop, c.n_fft};
