@@ -12,7 +12,7 @@ import os
 
 import torch  # noqa: F401  (loads libamdhip64 first)
 
-__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcSpkConfig", "AcSpkStages", "AcLmConfig", "AcLmLayout", "AcLmStages", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
+__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcSpkConfig", "AcSpkStages", "AcLmConfig", "AcLmLayout", "AcLmStages", "AcLmScoreStages", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
            "Handle", "HandleOwner"]
 
 AC_MAX_RATIOS = 8
@@ -195,6 +195,10 @@ class AcLmStages(C.Structure):
     _fields_ = [("q", C.c_void_p), ("attn", C.c_void_p), ("layer_out", C.c_void_p), ("final_norm", C.c_void_p)]
 
 
+class AcLmScoreStages(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("q", "k", "attn", "layer_out", "final_norm", "logits")]
+
+
 class AcKernelStat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 96),
@@ -314,6 +318,9 @@ EXPORTS = {
     "ac_lm_embed": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "ac_lm_forward": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp, _i, _vp, C.POINTER(AcLmStages), _vp, _sz, _vp]),
     "ac_lm_step": (_i, [_vp, _vp, _sz, _i, _i, _i, _ll, C.c_float, C.c_float, C.c_uint64, _vp, _vp, _sz, _vp]),
+    "ac_lm_prepare_score": (_i, [_vp]),
+    "ac_lm_score_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "ac_lm_score": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(AcLmScoreStages), _vp, _sz, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

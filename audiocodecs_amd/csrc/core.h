@@ -25,6 +25,8 @@
 //                   ac_spk_* entry points
 //   lm_path.hip     the Llama decoder with a KV cache (llama.h): plan, finalize, the state's layout, the launch sequences of a forward and of one
 //                   generated token, its kernels and the ac_lm_* entry points; the token draw goes through the public ac_sample_tokens
+//   lm_score.hip    the full-sequence scoring forward of the same decoder on the matrix pipe (llama_score.h): the packing of its matrices for
+//                   linear_rows, the launch sequence of a chunk of clips, its kernels and ac_lm_prepare_score / ac_lm_score
 //   ac_api.hip    the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
@@ -181,12 +183,17 @@ struct SpkPlan {                                       // spk_path.hip: WavLM x-
 
 struct LmLayer {
     size_t an = 0, fn = 0, wqkv = 0, wo = 0, w1 = 0, w3 = 0, w2 = 0;   // the two norm weights; [nq + 2 nkv hd][dim] (q | k | v), [dim][nq], [ffn][dim] x 2, [dim][ffn]; fp32, no biases
+    PackedGemm g_qkv, g_o, g_13, g_2;                  // lm_score.hip (ac_lm_prepare_score): the same matrices for linear_rows, w1 | w3 stacked [2 ffn][dim]
 };
 
 struct LmPlan {                                        // lm_path.hip: Llama decoder with a KV cache
     size_t emb = 0, prompt = 0, norm = 0, head = 0;    // [codebooks * vocab][dim], [dim][prompt_dim], [dim], [codebooks][vocab][dim]
     size_t rope_cos = 0, rope_sin = 0;                 // [2 * max_seq_len][head_dim / 2]: the caller's table
     std::vector<LmLayer> layers;
+    // lm_score.hip: set by ac_lm_prepare_score.  The heads as llama_score.h's operand image [codebooks][Cpad / 16][k-steps][2][64][8]
+    bool score_ready = false;
+    size_t head_img = 0, head_inv = 0;
+    int head_cpad = 0, head_ksteps = 0;
 };
 
 struct ProfRec {

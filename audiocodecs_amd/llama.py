@@ -13,6 +13,12 @@ about 5e-4 rad: a kernel that recomputed the angle would not reproduce it).
 strictly linear graph of ``STEPS_PER_REPLAY`` steps which reads its position from the state; ``alive`` is polled with a non-blocking copy
 once per replay, never per token, and steps that run after every row has ended change nothing that is returned.
 
+``score`` is the teacher-forced pass of the recipes' validation and test loops: one causal forward over
+``[prompt | toks]`` on the matrix pipe, the log-probability of every target and the arg-max of every row, without logits in memory.
+
+With ``input_dim`` set (the recipes' task files) the checkpoint has ``tok_embeddings.weight`` of that width and the ``input`` Linear behind
+it; the two are folded on the host into the one ``[num_codebooks * vocab_size, dim]`` table the library reads (`fold_input`).
+
 Refused (none of the recipes uses them): a finite ``eos_threshold``, ``use_kv_cache=False``, ``batch_parallel=False``, a mask other than
 ``"causal"``, ``embedding_kwargs``, a prompt whose length is no multiple of ``num_codebooks``, prompt + ``bos_toks`` + ``max_gen_toks``
 beyond ``2 * max_seq_len`` (where the reference's rotary table ends), a vocabulary outside the sampler's 2..16384 and more than 64 rows
@@ -33,10 +39,12 @@ from . import _native
 from . import prng
 from .sampling import MAX_VOCAB, MIN_VOCAB, STREAM
 
-__all__ = ["LlamaConfig", "LLAMA_TTS", "LLAMA_TINY", "LlamaDecoder", "LlamaState", "stack_generated", "rope_table", "MAX_ROWS", "STEPS_PER_REPLAY"]
+__all__ = ["LlamaConfig", "LLAMA_TTS", "LLAMA_TINY", "LlamaDecoder", "LlamaState", "LlamaScore", "IGNORE", "stack_generated", "rope_table", "fold_input", "MAX_ROWS",
+           "STEPS_PER_REPLAY"]
 
 MAX_ROWS = 64               # rows (batch entries) per state
 STEPS_PER_REPLAY = 16       # generated tokens per graph replay = per poll of `alive`
+IGNORE = -1                 # a target of `score` that marks an unscored position (any id outside [0, vocab_size) does)
 
 
 @dataclass(frozen=True)
@@ -55,6 +63,7 @@ class LlamaConfig:
     prompt_dim: Optional[int] = None
     num_codebooks: int = 2
     embedding_kwargs: Optional[dict] = None
+    input_dim: Optional[int] = None
 
     @property
     def head_dim(self) -> int:
@@ -104,11 +113,48 @@ def weight_names(cfg: LlamaConfig):
     names += [f"output.{k}.weight" for k in range(cfg.num_codebooks)] if cfg.num_codebooks > 1 else ["output.weight"]
     if cfg.prompt_dim:
         names.append("prompt.weight")
+    if cfg.input_dim is not None:
+        names.append("input.weight")
     for l in range(cfg.n_layers):
         names += [f"layers.{l}.attention.{w}.weight" for w in ("wq", "wk", "wv", "wo")]
         names += [f"layers.{l}.feed_forward.{w}.weight" for w in ("w1", "w2", "w3")]
         names += [f"layers.{l}.attention_norm.weight", f"layers.{l}.ffn_norm.weight"]
     return names
+
+
+def fold_input(table: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """``input(tok_embeddings(tok))`` as one table: `table` [rows, input_dim] times `weight` [dim, input_dim] transposed, the product in
+    fp64 and rounded once to fp32 -- every row of the result is the correctly rounded embedding of its id."""
+    if table.dim() != 2 or weight.dim() != 2 or table.shape[1] != weight.shape[1]:
+        raise ValueError(f"`tok_embeddings.weight` {tuple(table.shape)} and `input.weight` {tuple(weight.shape)} do not share the width input_dim")
+    return (table.detach().cpu().double() @ weight.detach().cpu().double().T).to(torch.float32).contiguous()
+
+
+@dataclass
+class LlamaScore:
+    """What `LlamaDecoder.score` returns; every tensor stays on the device.  `stages` is None unless they were asked for."""
+
+    logp: torch.Tensor          # [B, T] fp32: log_softmax(logits)[target], 0 where unscored
+    pred: torch.Tensor          # [B, T] int64: the arg-max of every row's logits, the lowest index on a tie
+    sum_logp: torch.Tensor      # [B] fp64: logp summed over the row's scored positions, in a fixed order
+    count: torch.Tensor         # [B] int64: scored positions
+    errors: torch.Tensor        # [B] int64: scored positions with pred != target
+    stages: Optional[dict] = None
+
+    @property
+    def nll(self) -> torch.Tensor:
+        """Mean negative log-likelihood over all scored positions (the recipes' loss)."""
+        return -self.sum_logp.sum() / self.count.sum()
+
+    @property
+    def ter(self) -> torch.Tensor:
+        """Token error rate of the arg-max over all scored positions."""
+        return self.errors.sum().double() / self.count.sum()
+
+    @property
+    def mean_logp(self) -> torch.Tensor:
+        """[B]: the length-normalised log-probability of every row."""
+        return self.sum_logp / self.count
 
 
 def stack_generated(hyp_toks, num_codebooks: int, vocab_size: int) -> torch.Tensor:
@@ -186,6 +232,11 @@ class LlamaDecoder(_native.HandleOwner):
         if missing:
             raise KeyError(f"the state dict lacks {len(missing)} keys of a LlamaDecoder of this configuration, first: {missing[:3]}")
         self._weights = {k: state_dict[k] for k in weight_names(config)}
+        if config.input_dim is not None:      # the library knows one table of width dim: E @ W^T
+            if tuple(self._weights["tok_embeddings.weight"].shape) != (config.num_codebooks * config.vocab_size, config.input_dim):
+                raise ValueError(f"`tok_embeddings.weight` must be [{config.num_codebooks * config.vocab_size}, {config.input_dim}] with input_dim set")
+            self._weights["tok_embeddings.weight"] = fold_input(self._weights["tok_embeddings.weight"], self._weights.pop("input.weight"))
+        self._scoring = set()
         self._weights["lm.rope_cos"], self._weights["lm.rope_sin"] = rope_table(config)
         self._natives = {}
         self._warm = set()
@@ -224,6 +275,83 @@ class LlamaDecoder(_native.HandleOwner):
         with torch.cuda.device(toks.device):
             rc = nat.lib.ac_lm_embed(nat.h, _native._ptr(t64) if T else None, B, T, curr_pos, _native._ptr(pe), P, width, _native._ptr(out), _native._stream())
         _native.check(rc, nat.h, "ac_lm_embed")
+        return out
+
+    # ---- score ---------------------------------------------------------------------------------------------------------------------
+    def _check_score(self, toks, targets, prompt_embs, lengths):
+        """The refusals of `score` that need no device -> (B, T, P)."""
+        cfg = self.config
+        if not torch.is_tensor(toks) or toks.dim() != 2 or toks.is_floating_point() or toks.dtype == torch.bool or toks.shape[0] < 1 or toks.shape[1] < 1:
+            raise ValueError("`toks` must be a [B, T] tensor of an integer dtype with B, T >= 1")
+        B, T = (int(n) for n in toks.shape)
+        if not torch.is_tensor(targets) or targets.dtype != torch.int64 or tuple(targets.shape) != (B, T):
+            raise ValueError(f"`targets` must be a [{B}, {T}] int64 tensor")
+        P = 0
+        if prompt_embs is not None:
+            if not torch.is_tensor(prompt_embs) or prompt_embs.dim() != 3 or prompt_embs.shape[0] != B or prompt_embs.dtype != torch.float32:
+                raise ValueError(f"`prompt_embs` must be a [{B}, P, width] fp32 tensor")
+            P = int(prompt_embs.shape[1])
+            if P % cfg.num_codebooks:
+                raise ValueError(f"a prompt of {P} rows is no multiple of num_codebooks ({cfg.num_codebooks})")
+        if P + T > 2 * cfg.max_seq_len:
+            raise ValueError(f"prompt + toks = {P + T} positions pass 2 * max_seq_len = {2 * cfg.max_seq_len}, where the rotary table ends")
+        if lengths is not None:
+            if torch.is_tensor(lengths):
+                if lengths.is_floating_point() or lengths.dtype == torch.bool or tuple(lengths.shape) != (B,):
+                    raise ValueError(f"`lengths` must be [{B}] integers")
+                host = None if lengths.is_cuda else lengths.tolist()
+            else:
+                host = list(lengths)
+                if len(host) != B or any(isinstance(n, bool) or not isinstance(n, int) for n in host):
+                    raise ValueError(f"`lengths` must be [{B}] integers")
+            if host is not None and any(not 0 <= n <= T for n in host):
+                raise ValueError(f"`lengths` must lie in 0..{T}")
+        return B, T, P
+
+    @torch.no_grad()
+    def score(self, toks: torch.Tensor, targets: torch.Tensor, *, prompt_embs: torch.Tensor = None, lengths=None, return_stages: bool = False,
+              _chunk_clips: int = None) -> LlamaScore:
+        """Teacher-forced scoring: one causal forward over ``embed(toks, prompt_embs, 0)``; position t of row b is scored against
+        ``targets[b, t]`` (int64) from the logits of row ``P + t``.  A target outside ``[0, vocab_size)`` (`IGNORE`) and positions
+        ``t >= lengths[b]`` are unscored.  `lengths` is [B] integers: given on the host they are checked against 0..T; a device tensor is
+        not read back, the kernels clamp it into 0..T.  Nothing is read back and the call may be captured into a graph once it ran plain
+        on that device.  `return_stages` adds, per layer, the rotated "q" and "k", "attn" and "layer_out" over all P + T rows, then
+        "final_norm" and the "logits" [B, T, vocab_size] of the token rows (for tests).  `_chunk_clips` (developer argument) forces the
+        clips per pass; the results do not depend on it."""
+        cfg = self.config
+        B, T, P = self._check_score(toks, targets, prompt_embs, lengths)
+        _host.need_cuda(toks.is_cuda and targets.is_cuda, "llama", "tokens and targets")
+        if targets.device != toks.device:
+            raise ValueError(f"`targets` ({targets.device}) and `toks` ({toks.device}) must be on one device")
+        embs = self.embed(toks, prompt_embs if P else None, 0)
+        dev, Ttot = embs.device, P + T
+        nat = self._native_for(embs)
+        if dev.index not in self._scoring:
+            with torch.cuda.device(dev):
+                _native.check(nat.lib.ac_lm_prepare_score(nat.h), nat.h, "ac_lm_prepare_score")
+            self._scoring.add(dev.index)
+        tg = targets.contiguous()
+        ln = None
+        if lengths is not None:
+            ln = (lengths if torch.is_tensor(lengths) else torch.tensor(lengths, dtype=torch.int64)).to(device=dev, dtype=torch.int64).contiguous()
+        out = LlamaScore(torch.empty(B, T, dtype=torch.float32, device=dev), torch.empty(B, T, dtype=torch.int64, device=dev),
+                         torch.empty(B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev))
+        st = None
+        if return_stages:
+            nq, nkvd, L = cfg.n_heads * cfg.head_dim, cfg.n_kv_heads * cfg.head_dim, cfg.n_layers
+            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
+            out.stages = {"q": new(L, B, Ttot, nq), "k": new(L, B, Ttot, nkvd), "attn": new(L, B, Ttot, nq), "layer_out": new(L, B, Ttot, cfg.dim),
+                          "final_norm": new(B, Ttot, cfg.dim), "logits": new(B, T, cfg.vocab_size)}
+            st = _native.AcLmScoreStages(*(out.stages[k].data_ptr() for k in ("q", "k", "attn", "layer_out", "final_norm", "logits")))
+        if _chunk_clips is not None and (isinstance(_chunk_clips, bool) or not isinstance(_chunk_clips, int) or _chunk_clips < 1):
+            raise ValueError("`_chunk_clips` must be a positive int")
+        need = int(nat.lib.ac_lm_score_workspace_bytes(nat.h, B if _chunk_clips is None else min(B, _chunk_clips), Ttot))
+        with torch.cuda.device(dev):
+            ws = nat.workspace(need + 256)
+            rc = nat.lib.ac_lm_score(nat.h, _native._ptr(embs), B, P, T, _native._ptr(tg), _native._ptr(ln), _native._ptr(out.logp), _native._ptr(out.pred),
+                                     _native._ptr(out.sum_logp), _native._ptr(out.count), _native._ptr(out.errors), C.byref(st) if st is not None else None,
+                                     _native._ptr(ws), need + 256, _native._stream())
+        _native.check(rc, nat.h, "ac_lm_score")
         return out
 
     # ---- forward -------------------------------------------------------------------------------------------------------------------

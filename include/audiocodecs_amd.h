@@ -837,6 +837,38 @@ int ac_lm_forward(ac_handle* h, void* state_dev, size_t state_bytes, int B, int 
 int ac_lm_step(ac_handle* h, void* state_dev, size_t state_bytes, int B, int capacity, int max_steps, long long eos_id, float temp, float top_p,
                uint64_t key, float* logits_log, void* ws, size_t ws_bytes, void* stream);
 
+/* Scoring token sequences teacher-forced: one causal forward over all P + T rows of every clip on the matrix
+ * pipe (split16 arithmetic, per-row scales), without a state and without the 64-row limit of one.  The [B][T][vocab] logits are never
+ * written: the output head keeps a running maximum, the sum of exponentials, the target's logit and the arg-max per row.
+ *   ac_lm_prepare_score          once per handle before the first ac_lm_score (idempotent; SYNCHRONISES the device and reallocates the
+ *                                handle's weights -- not to be called while work of the handle is in flight or being captured): packs
+ *                                wq | wk | wv, wo, w1 | w3 and w2 of every layer for the tap-GEMM and the output heads for the head kernel.
+ *                                The fp32 matrices of ac_lm_forward / ac_lm_step stay.  AC_EINVAL unless the matrices have rows in
+ *                                multiples of 64 or 96 and columns in multiples of 32, the head dim is a multiple of 16 up to 128 and
+ *                                dim <= 2048.
+ *   ac_lm_score_workspace_bytes  for B clips of T_total = P + T rows: the clips of one pass are capped so that it stays near 1 GiB.
+ *   ac_lm_score                  embs [B][P + T][dim] (ac_lm_embed's output), targets [B][T] int64, lengths [B] int64 or NULL.  Position t
+ *                                of clip b is scored against targets[b][t] from the logits of row P + t (output head t % num_codebooks;
+ *                                P has to be a multiple of num_codebooks) when the target lies in [0, vocab_size) and t < lengths[b]
+ *                                (clamped into 0..T).  logp [B][T] = log_softmax(logits)[target], 0 where unscored; pred [B][T] int64 the
+ *                                arg-max of every position, the lowest index on a tie; sum_logp [B] fp64 the scored log-probs summed in
+ *                                a fixed order, count [B] and errors [B] int64 the scored positions and those with pred != target.  The
+ *                                batch is walked in chunks of as many whole clips as `ws_bytes` holds; a clip's results do not depend on
+ *                                the chunking.  Nothing is read back and nothing synchronises: the call may be captured. */
+typedef struct ac_lm_score_stages {  /* optional outputs of ac_lm_score, each pointer may be NULL */
+    float* q;            /* [layers][B][P + T][n_heads * head_dim]      rotated queries              */
+    float* k;            /* [layers][B][P + T][n_kv_heads * head_dim]   rotated keys                 */
+    float* attn;         /* [layers][B][P + T][n_heads * head_dim]      attention output (before wo) */
+    float* layer_out;    /* [layers][B][P + T][dim]                     the layer's output           */
+    float* final_norm;   /* [B][P + T][dim]                             the final RMSNorm            */
+    float* logits;       /* [B][T][vocab]                               the logits of the token rows */
+} ac_lm_score_stages;
+int ac_lm_prepare_score(ac_handle* h);
+size_t ac_lm_score_workspace_bytes(const ac_handle* h, int B, int T_total);
+int ac_lm_score(ac_handle* h, const float* embs_dev, int B, int P, int T, const int64_t* targets_dev, const int64_t* lengths_dev, float* logp_out,
+                int64_t* pred_out, double* sum_logp_out, int64_t* count_out, int64_t* errors_out, const ac_lm_score_stages* stages, void* ws,
+                size_t ws_bytes, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
