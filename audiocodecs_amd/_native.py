@@ -12,7 +12,7 @@ import os
 
 import torch  # noqa: F401  (loads libamdhip64 first)
 
-__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcSpkConfig", "AcSpkStages", "AcLmConfig", "AcLmLayout", "AcLmStages", "AcLmScoreStages", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
+__all__ = ["lib", "lib_path", "AcConfig", "AcMimiConfig", "AcDacConfig", "AcWavtokConfig", "AcVocosConfig", "AcSpkConfig", "AcSpkStages", "AcLmConfig", "AcLmLayout", "AcLmStages", "AcLmScoreStages", "AcProbeConfig", "AcProbeOutputs", "AcKernelStat", "NativeError", "check", "EXPORTS", "track", "set_precision", "check_precision", "PRECISIONS",
            "Handle", "HandleOwner"]
 
 AC_MAX_RATIOS = 8
@@ -199,6 +199,15 @@ class AcLmScoreStages(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("q", "k", "attn", "layer_out", "final_norm", "logits")]
 
 
+class AcProbeConfig(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("struct_size", "vocab_size", "num_codebooks", "embedding_dim", "hidden_size", "num_layers", "pooling", "head", "num_classes",
+                                         "blank_id", "padding_idx", "device")]
+
+
+class AcProbeOutputs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("frame_pred", "hyp_toks", "hyp_lens", "log_probs", "pred", "pooled", "layer_out", "logits")]
+
+
 class AcKernelStat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 96),
@@ -321,6 +330,9 @@ EXPORTS = {
     "ac_lm_prepare_score": (_i, [_vp]),
     "ac_lm_score_workspace_bytes": (_sz, [_vp, _i, _i]),
     "ac_lm_score": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(AcLmScoreStages), _vp, _sz, _vp]),
+    "ac_probe_create": (_i, [C.POINTER(AcProbeConfig), C.POINTER(_vp)]),
+    "ac_probe_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "ac_probe_forward": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(AcProbeOutputs), _vp, _sz, _vp]),
     "ac_profile_begin": (_i, [_vp]),
     "ac_profile_end": (_i, [_vp, C.POINTER(AcKernelStat), _i]),
     "ac_debug_clock": (_i, [_vp, _i, C.POINTER(C.c_double)]),

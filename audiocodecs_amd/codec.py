@@ -197,6 +197,19 @@ class Codec(torch.nn.Module, ABC):
         matching_set = torch.cat([self.sig_to_feats(s[None] if s.dim() == 1 else s).flatten(end_dim=-2) for s in spk_sigs])
         return self.feats_to_sig(knn_match(self.toks_to_qfeats(toks), matching_set, topk))
 
+    def probe(self, sig, probe, length=None):
+        """`sig_to_toks`, then a `TokenProbe` (probe.py) over the tokens -> its `ProbeOutput`.  `length` is relative, as everywhere in this
+        class; the probe gets round(length * N) frames per clip (`probe.relative_to_frames`), computed on the device.  Built from the
+        public methods only."""
+        from .probe import relative_to_frames
+
+        toks = self.sig_to_toks(sig, length)
+        if length is None:
+            return probe.forward(toks)
+        if not torch.is_tensor(length):
+            length = torch.as_tensor(length, dtype=torch.float32)
+        return probe.forward(toks, relative_to_frames(length.to(toks.device), toks.shape[1]))
+
     def _resynthesize(self, sig, length):
         """`sig_to_toks`, `toks_to_sig` and the length adjustment of downstream/test_sr.py:89-100 (the decode is replicate-padded or narrowed
         to the input's length): (toks [B, N, K], hyp [B, T])."""

@@ -172,6 +172,11 @@ int ac_finalize(ac_handle* h) {
         if (int rc = lm_finalize(h, pk)) return rc;
         return upload_blob(h, pk, h->lcfg.device);
     }
+    if (h->arch == ARCH_PROBE) {
+        Packer pk{h};
+        if (int rc = probe_finalize(h, pk)) return rc;
+        return upload_blob(h, pk, h->pcfg.device);
+    }
     const ac_config& c = h->cfg;
     Arch a = make_arch(c);
     Packer pk{h};
@@ -372,6 +377,7 @@ int ac_quantize_ws(ac_handle* h, const float* feats, int B, int N, int K, int64_
     if (rc) return rc;
     if (h->arch == ARCH_SPK) return fail(h, AC_EINVAL, "ac_quantize: a speaker-encoder handle has no quantizer");
     if (h->arch == ARCH_LM) return fail(h, AC_EINVAL, "ac_quantize: a Llama decoder handle has no quantizer");
+    if (h->arch == ARCH_PROBE) return fail(h, AC_EINVAL, "ac_quantize: a token-probe handle has no quantizer");
     if (!feats || !toks || B < 1 || N < 1 || K < 1 || K > num_q(h)) return fail(h, AC_EINVAL, "ac_quantize: bad argument");
     if (h->wt.vocos) return fail(h, AC_ESTATE, "ac_quantize: a Vocos handle decodes only (its tables are not a quantizer)");
     pool_bind(h, nullptr, 0, 0);      // (EnCodec / DAC: the codebook search runs outside split-operand arithmetic)
@@ -398,6 +404,7 @@ int ac_dequantize_ws(ac_handle* h, const int64_t* toks, int B, int N, int K, flo
     if (rc) return rc;
     if (h->arch == ARCH_SPK) return fail(h, AC_EINVAL, "ac_dequantize: a speaker-encoder handle has no quantizer");
     if (h->arch == ARCH_LM) return fail(h, AC_EINVAL, "ac_dequantize: a Llama decoder handle has no quantizer");
+    if (h->arch == ARCH_PROBE) return fail(h, AC_EINVAL, "ac_dequantize: a token-probe handle has no quantizer");
     if (!qfeats || !toks || B < 1 || N < 1 || K < 1 || K > num_q(h)) return fail(h, AC_EINVAL, "ac_dequantize: bad argument");
     pool_bind(h, nullptr, 0, 0);
     if (h->arch == ARCH_DAC) return dac_from_codes(h, (hipStream_t)stream, reinterpret_cast<const long long*>(toks), B * N, K, qfeats);
@@ -486,6 +493,7 @@ int ac_embs(ac_handle* h, int K, float* embs, void* stream) {
     if (rc) return rc;
     if (h->arch == ARCH_SPK) return fail(h, AC_EINVAL, "ac_embs: a speaker-encoder handle has no codebooks");
     if (h->arch == ARCH_LM) return fail(h, AC_EINVAL, "ac_embs: a Llama decoder handle has no codebooks (ac_lm_embed)");
+    if (h->arch == ARCH_PROBE) return fail(h, AC_EINVAL, "ac_embs: a token-probe handle has no codebooks");
     if (!embs || K < 1 || K > num_q(h)) return fail(h, AC_EINVAL, "ac_embs: bad argument");
     size_t n, off;
     if (h->arch == ARCH_MIMI) { n = (size_t)K * h->mcfg.codebook_size * h->mcfg.codebook_dim; off = h->mimi.cb_plain; }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build libaudiocodecs_amd.so for gfx950 (MI355X) in-tree.  Usage: build.sh [extra hipcc flags]
-# Seventeen translation units (core.h has the map), compiled in parallel, linked into one shared library.
+# Eighteen translation units (core.h has the map), compiled in parallel, linked into one shared library.
 # -fno-slp-vectorize: the SLP vectoriser turns the stem's scalar fp32 FMAs (enc_front.h) into v_pk_fma_f32 with op_sel
 # broadcasts, and THAT code returned wrong values in lanes 48..63 of one FMA group per ~100 chunks whenever a second wave shared the
 # SIMD (run-to-run different; never with one wave per SIMD, never without the packed FMAs -- profiles/r3_pk_fma_hazard.md).
@@ -33,7 +33,7 @@ case "$hipcc_ver" in
 esac
 mkdir -p "$obj" "$obj/dev"
 pids=()
-TUS=(core mimi_path mimi_stream encodec_stream dac_path wavtok_path stream_path knn specdist stoi dnsmos tokstats sampling spk_path lm_path lm_score ac_api)
+TUS=(core mimi_path mimi_stream encodec_stream dac_path wavtok_path stream_path knn specdist stoi dnsmos tokstats sampling spk_path lm_path lm_score probe_path ac_api)
 # -save-temps=obj: the device assembly of every translation unit stays beside its object for tools/mfma_branch_hazard.py (below)
 for tu in "${TUS[@]}"; do
     "$HIPCC" "${FLAGS[@]}" -save-temps=obj -c "$here/$tu.hip" -o "$obj/$tu.o" &

@@ -27,6 +27,9 @@
 //                   generated token, its kernels and the ac_lm_* entry points; the token draw goes through the public ac_sample_tokens
 //   lm_score.hip    the full-sequence scoring forward of the same decoder on the matrix pipe (llama_score.h): the packing of its matrices for
 //                   linear_rows, the launch sequence of a chunk of clips, its kernels and ac_lm_prepare_score / ac_lm_score
+//   probe_path.hip  the TokenProbe (bilstm.h, probe.h): multi-codebook embedding and pooling, a bidirectional length-aware LSTM with one launch per
+//                   step, a CTC head with greedy collapse or an utterance head with masked statistics pooling; plan, finalize, the launch
+//                   sequence of a chunk of clips and the ac_probe_* entry points; the matrix products are linear_rows
 //   ac_api.hip    the extern "C" entry points of include/audiocodecs_amd.h
 // This header declares; it includes no header that defines a non-template kernel.
 #pragma once
@@ -196,6 +199,15 @@ struct LmPlan {                                        // lm_path.hip: Llama dec
     int head_cpad = 0, head_ksteps = 0;
 };
 
+struct ProbePlan {                                     // probe_path.hip: TokenProbe
+    size_t table = 0, wlin = 0, score = 0;             // embedding [K C (+ 1)][E]; LinearPooling's [K]; AttentionalPooling's folded scores [K C + 2]
+    std::vector<PackedGemm> ih;                        // per layer: W_ih of both directions stacked [8H][in] with b_ih + b_hh
+    std::vector<size_t> hh;                            // per layer: W_hh of both directions in MFMA B-fragment order [2][H/4][H/16][64][4]
+    PackedGemm head;                                   // CTC head [cpad][2H] + bias: zero rows beyond num_classes
+    size_t head_w = 0, head_b = 0;                     // utterance head [num_classes][4H], [num_classes] (fp32, read by probe_utt_head_kernel)
+    int cpad = 0;
+};
+
 struct ProfRec {
     int name_id;
     int count;
@@ -207,7 +219,7 @@ struct ProfRec {
 }  // namespace acimpl
 using namespace acimpl;
 
-enum { ARCH_ENCODEC = 0, ARCH_MIMI = 1, ARCH_DAC = 2, ARCH_WAVTOK = 3, ARCH_SPK = 4, ARCH_LM = 5 };
+enum { ARCH_ENCODEC = 0, ARCH_MIMI = 1, ARCH_DAC = 2, ARCH_WAVTOK = 3, ARCH_SPK = 4, ARCH_LM = 5, ARCH_PROBE = 6 };
 
 struct ac_handle {
     int arch = ARCH_ENCODEC;
@@ -222,6 +234,8 @@ struct ac_handle {
     SpkPlan spk;
     ac_lm_config lcfg{};
     LmPlan lm;
+    ac_probe_config pcfg{};
+    ProbePlan probe;
     std::string err;
     std::map<std::string, std::vector<float>> host;
     bool finalized = false;
@@ -1165,6 +1179,7 @@ Workspace wavtok_plan_ws(const ac_handle* h, int B, int T_in, int N_frames, bool
 int wavtok_decoder_fwd(ac_handle* h, hipStream_t st, const float* feats, int B, int N, float* sig, WsPtrs& ws);
 int spk_finalize(ac_handle* h, Packer& pk);             // spk_path.hip
 int lm_finalize(ac_handle* h, Packer& pk);              // lm_path.hip
+int probe_finalize(ac_handle* h, Packer& pk);           // probe_path.hip
 int upload_blob(ac_handle* h, Packer& pk, int device);
 constexpr int DAC_CODE_DIM = 8;   // = DAC_D (dac.h), asserted in dac_path.hip
 

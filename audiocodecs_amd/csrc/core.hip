@@ -1304,6 +1304,7 @@ int check_ready(ac_handle* h) {
 int check_len(ac_handle* h, long long samples) {
     if (h->arch == ARCH_SPK) return fail(h, AC_EINVAL, "a speaker-encoder handle has no codec entry points (ac_spk_embed)");
     if (h->arch == ARCH_LM) return fail(h, AC_EINVAL, "a Llama decoder handle has no codec entry points (ac_lm_forward, ac_lm_step)");
+    if (h->arch == ARCH_PROBE) return fail(h, AC_EINVAL, "a token-probe handle has no codec entry points (ac_probe_forward)");
     const long long lim = 0x70000000LL / (h->arch == ARCH_DAC ? 512 : 256) - 1;
     if (samples > lim) return fail(h, AC_EINVAL, "clip of %lld samples is too long for one call (limit %lld): split it", samples, lim);
     return AC_OK;

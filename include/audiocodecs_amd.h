@@ -869,6 +869,55 @@ int ac_lm_score(ac_handle* h, const float* embs_dev, int B, int P, int T, const 
                 int64_t* pred_out, double* sum_logp_out, int64_t* count_out, int64_t* errors_out, const ac_lm_score_stages* stages, void* ws,
                 size_t ws_bytes, void* stream);
 
+/* TokenProbe: the downstream recipes' probe over codec tokens -- multi-codebook embedding and pooling, a
+ * bidirectional LSTM over packed sequences, and a CTC head with greedy decode or an utterance head over masked statistics pooling.
+ * One more handle kind: ac_probe_create, ac_load_weights under the names below, ac_finalize, then ac_probe_forward; ac_destroy frees it.
+ * AC_EINVAL from ac_probe_create unless hidden_size is a multiple of 32 up to 1024, embedding_dim (the input width) a multiple of 32,
+ * num_layers in 1..8, num_codebooks in 1..32 and the enumerations are known; ac_finalize refuses exact-product arithmetic
+ * (AC_PRECISION_FP32_EXACT): the input projections run as split16 row-mode GEMMs only.
+ * Tensors (fp32): "embedding.weight" [K C (+ 1 with padding_idx)][E]; AC_PROBE_POOL_LINEAR: "pooling.mlp.weight" [K] (absent with K = 1);
+ * AC_PROBE_POOL_ATTENTIONAL: "pooling.score" [K C + 2], the score w2 . relu(W1 e + b1) of every table row folded by the caller, entry K C
+ * the padding row's and entry K C + 1 a zero row's; "encoder.rnn.{weight_ih,weight_hh,bias_ih,bias_hh}_l<n>" and "..._l<n>_reverse";
+ * "head.weight" [num_classes][2H] (CTC) or [num_classes][4H] (utterance: mean columns, then std columns), "head.bias".
+ *   ac_probe_workspace_bytes  for B clips of N frames: the clips of one pass are capped so that it stays near 1 GiB.
+ *   ac_probe_forward          input: int64 ids [B][N][K], or fp32 features [B][N][E] with AC_PROBE_POOL_NONE.  lengths [B] int64 absolute
+ *                             frame counts or NULL (all N), clamped into 0..N on the device.  An id equal to vocab_size with padding_idx
+ *                             reads row K C; any other id outside [0, vocab_size) reads a zero row, indexes nothing and raises the handle's
+ *                             sticky bad-token word (reported by the next entry point or ac_poll_status).  The backward direction of clip b
+ *                             starts at frame lengths[b] - 1; frames beyond a length are zero in every layer output.  The batch is walked
+ *                             in chunks of as many whole clips as `ws_bytes` holds; a clip's results do not depend on its batch or the
+ *                             chunking.  Nothing is read back and nothing synchronises: the call may be captured. */
+enum { AC_PROBE_POOL_NONE = 0, AC_PROBE_POOL_LINEAR = 1, AC_PROBE_POOL_ATTENTIONAL = 2 };
+enum { AC_PROBE_HEAD_CTC = 0, AC_PROBE_HEAD_UTTERANCE = 1 };
+typedef struct ac_probe_config {
+    int32_t struct_size;      /* sizeof(ac_probe_config) */
+    int32_t vocab_size;       /* C: ids per codebook (ignored with AC_PROBE_POOL_NONE) */
+    int32_t num_codebooks;    /* K */
+    int32_t embedding_dim;    /* E: the LSTM's input width */
+    int32_t hidden_size;      /* H per direction */
+    int32_t num_layers;
+    int32_t pooling;          /* AC_PROBE_POOL_* */
+    int32_t head;             /* AC_PROBE_HEAD_* */
+    int32_t num_classes;
+    int32_t blank_id;         /* CTC */
+    int32_t padding_idx;      /* 0 / 1: the table has the extra row K C, read by the id vocab_size */
+    int32_t device;
+} ac_probe_config;
+typedef struct ac_probe_outputs {  /* CTC: frame_pred, hyp_toks, hyp_lens required; utterance: log_probs, pred required; the rest may be NULL */
+    int64_t* frame_pred;   /* CTC [B][N]: per-frame arg-max (lowest index on a tie), -1 beyond the length                    */
+    int64_t* hyp_toks;     /* CTC [B][N]: repeats collapsed, blanks removed, left-packed, -1 filled                         */
+    int64_t* hyp_lens;     /* CTC [B]                                                                                       */
+    float* log_probs;      /* CTC [B][N][num_classes] (optional; zero beyond the length); utterance [B][num_classes]         */
+    int64_t* pred;         /* utterance [B]                                                                                 */
+    float* pooled;         /* stage [B][N][E]: the pooled embeddings (ignored with AC_PROBE_POOL_NONE)                      */
+    float* layer_out;      /* stage [layers][B][N][2H]                                                                      */
+    float* logits;         /* stage: CTC [B][N][num_classes], utterance [B][num_classes]                                    */
+} ac_probe_outputs;
+int ac_probe_create(const ac_probe_config* cfg, ac_handle** out);
+size_t ac_probe_workspace_bytes(const ac_handle* h, int B, int N);
+int ac_probe_forward(ac_handle* h, const void* input_dev, int B, int N, const int64_t* lengths_dev, const ac_probe_outputs* out, void* ws,
+                     size_t ws_bytes, void* stream);
+
 /* Optional per-kernel timing with HIP events on the caller's stream (bench.py's roofline leg).
  * ac_profile_begin arms it; every launch made by subsequent calls is bracketed by events.
  * ac_profile_end synchronises those events and writes up to `cap` records; returns the count. */
